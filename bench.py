@@ -2,6 +2,7 @@
 Benchmark of the ELBO hot path: site-log_prob evals/sec and ELBO step wall time on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c1|c3|c4|c5]
+                    [--dump-outputs DIR] [--full]
 
 One *step* = ``optimizer.zero_grad()`` + ELBO forward + backward (+ one RCCL all-reduce of the guide
 gradients when N > 1) + ``Adam.step()``, as in the reference's training loop (README.md:66-69).
@@ -9,11 +10,18 @@ The default workload is C2 (BASELINE.json configs[1]): the README biased-coin mo
 observations and 4096 Monte-Carlo particles per GPU (particles are sharded across GPUs: weak
 scaling). One site-log_prob eval = one (particle, site, observed element) triple.
 
-Prints ONE JSON line (rank 0) with the metric, the roofline of the dominant kernel (timed by span
-stamps -- every workgroup of exactly that kernel folds its start and end device clock into a slot
--- in replays of a capture of the same step, after the timed region; HIP events around the kernel
-only for eager runs) and the CPU baseline (the reference's torch-CPU semantics, oracle/cpu_port.py,
-on a bounded sample, N = 1 only).
+A plain run sets up the workload, warms up, times the K steps (``ms_per_step``, ``value``) and
+prints ONE JSON line (rank 0) with the metric. ``--dump-outputs DIR`` also writes what the last
+timed step computed (its loss, the guide parameters after it and their gradients) as
+``DIR/<name>.npy``; the inputs and, with this option, the number of steps before the timed ones
+depend on the arguments alone, so two builds can be compared output for output.
+
+``--full`` adds everything else to that line, each in runs of its own outside the timed region:
+timed eager steps, the roofline of the dominant kernel (timed by span stamps -- every workgroup of
+exactly that kernel folds its start and end device clock into a slot -- in replays of a capture of
+the same step; HIP events around the kernel only for eager runs), C2's reducible floor, the CPU
+baseline (the reference's torch-CPU semantics, oracle/cpu_port.py, on a bounded sample, N = 1
+only) and, for the default C2 run, the other configurations (``other_configs``).
 """
 from __future__ import annotations
 
@@ -203,6 +211,32 @@ def wait_device(device) -> None:
     while not event.query():
         if time.perf_counter() - t0 > 0.02:
             time.sleep(20e-6)
+
+
+# --dump-outputs: at most this much array data in all (the option's limit is 64 MB: room for the
+# .npy headers), and the steps that replace the time-filled graph warm-up (600 C2 steps ~ 50 ms)
+DUMP_LIMIT_BYTES = 60 * 10 ** 6
+DUMP_WARM_STEPS = 600
+
+
+def dump_outputs(directory, tensors):
+    """Write each tensor as ``directory/<name>.npy`` (float32, or float64 if it is one). An array
+    over its equal share of DUMP_LIMIT_BYTES is cut to a fixed sample of its flattened elements
+    (sorted indices drawn without replacement by numpy's default_rng(0): the same for every run
+    of the same shapes)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(tensors))
+    for name, tensor in tensors.items():
+        tensor = tensor.detach().cpu()
+        if tensor.dtype != torch.float64:
+            tensor = tensor.float()
+        array = tensor.numpy()
+        if array.nbytes > share:
+            keep = np.random.default_rng(0).choice(array.size, share // array.itemsize,
+                                                   replace=False)
+            array = array.reshape(-1)[np.sort(keep)]
+        np.save(os.path.join(directory, name + ".npy"), array)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -490,8 +524,10 @@ def communicator(group, device, kind="rccl"):
     return _COMMUNICATOR
 
 
-def run_config(config, args, world, rank, device, group, steps, warmup, cpu_budget):
-    """Measure one workload (all ranks); rank 0 gets the bench line's dict."""
+def run_config(config, args, world, rank, device, group, steps, warmup, cpu_budget,
+               dump_dir=None):
+    """Measure one workload (all ranks); rank 0 gets the bench line's dict. With `dump_dir`, rank 0
+    writes the last timed step's outputs there (dump_outputs)."""
     arm(f"{config}: set-up")
     w = workload(config, device, world, rank)
     if args.particles_per_gpu:
@@ -567,10 +603,24 @@ def run_config(config, args, world, rank, device, group, steps, warmup, cpu_budg
             seconds = float(t)
         return seconds, out
 
-    def warm_replays(replay, count):
+    def step_outputs(loss):
+        """What a caller of the timed step holds after it: the loss it returned, the guide
+        parameters it updated and the gradients it left on them (copies: later steps overwrite
+        them)."""
+        tensors = {"loss": loss}
+        for name, parameter in module.named_parameters():
+            tensors["param." + name] = parameter
+            if parameter.grad is not None:
+                tensors["grad." + name] = parameter.grad
+        return {name: t.detach().clone() for name, t in tensors.items()}
+
+    def warm_replays(replay, count, per_replay=1):
         """`count` replays, then as many more as fill --warm-ms at the measured replay time: the
         timed replays start with the clocks and caches at their steady state. Every rank runs the
-        same number (the slowest rank's replay time): a sharded replay holds a collective."""
+        same number (the slowest rank's replay time): a sharded replay holds a collective. With
+        --dump-outputs the further replays are those of DUMP_WARM_STEPS steps instead, whatever
+        they take (`per_replay` steps each): the training state the timed steps start from, and so
+        the outputs, must not depend on a measured time."""
         t0 = time.perf_counter()
         for _ in range(count):
             replay()
@@ -583,6 +633,8 @@ def run_config(config, args, world, rank, device, group, steps, warmup, cpu_budg
             per = float(t)
         extra = 0 if args.warm_ms <= 0 else \
             min(10000, max(0, math.ceil((args.warm_ms / 1e3 - per * count) / per)))
+        if args.dump_outputs and args.warm_ms > 0:
+            extra = math.ceil(DUMP_WARM_STEPS / per_replay)
         for i in range(extra):
             replay()
             if i % 8 == 7:
@@ -593,21 +645,27 @@ def run_config(config, args, world, rank, device, group, steps, warmup, cpu_budg
         # detached: keep no autograd graph alive across steps (graph capture needs it)
         return full_step().detach()
 
-    # Eager steps: every kernel launched from Python (the kernel timing comes from these).
+    # Eager steps: every kernel launched from Python (the kernel timing comes from these). Timed
+    # when they are the run's own step mode (--eager), or beside the graph's with --full.
     arm(f"{config}: eager warm-up")
     for _ in range(warmup):
         eager_step()
     wait_device(device)
-    arm(f"{config}: timed eager steps")
     eager_steps = max(3, steps // 3) if args.graph else steps
     gc_clock = _GcClock()
-    with gc_clock:
-        eager_elapsed, loss = timed(eager_step, eager_steps)
-    # a copy: the sharded step's loss is a view into the gradient bucket, which later steps
-    # (the kernel-timed ones) overwrite
-    loss = loss.detach().clone()
-    eager_ms = 1e3 * eager_elapsed / eager_steps
-    wait_device(device)
+    eager_elapsed = eager_ms = None
+    dumped = None
+    if args.full or not args.graph:
+        arm(f"{config}: timed eager steps")
+        with gc_clock:
+            eager_elapsed, loss = timed(eager_step, eager_steps)
+        # a copy: the sharded step's loss is a view into the gradient bucket, which later steps
+        # (the kernel-timed ones) overwrite
+        loss = loss.detach().clone()
+        eager_ms = 1e3 * eager_elapsed / eager_steps
+        if dump_dir and not args.graph:
+            dumped = step_outputs(loss)
+        wait_device(device)
 
     def kernel_timed_steps():
         """--eager (and split-graph gloo) runs: the kernel durations from further eager steps with
@@ -648,9 +706,10 @@ def run_config(config, args, world, rank, device, group, steps, warmup, cpu_budg
         timing_graph.check()
         return samples
 
-    if not args.graph:
+    if args.full and not args.graph:
         kernel_timed_steps()
-    elapsed, mode = eager_elapsed * steps / eager_steps, "eager"
+    if not args.graph:
+        elapsed, mode = eager_elapsed, "eager"
     if args.graph:
         # The same step captured once into a hipGraph and replayed (mininf_amd.graph.StepGraph).
         # one replay = `repeat` consecutive steps (N = 1): each graph launch leaves the device
@@ -683,33 +742,39 @@ def run_config(config, args, world, rank, device, group, steps, warmup, cpu_budg
                 return bucket.loss()
 
         arm(f"{config}: graph warm-up replays")
-        warm_replays(graph_step, max(1, warmup // repeat))
+        warm_replays(graph_step, max(1, warmup // repeat), repeat)
         arm(f"{config}: timed graph replays ({steps // repeat} replays of {repeat} steps)")
         elapsed, loss = timed(graph_step, steps // repeat)
-        loss = loss.detach().clone()   # (see above; the graph's own output is static as well)
+        # a copy: the sharded step's loss is a view into the gradient bucket, and the graph's own
+        # output is static as well; later steps overwrite both
+        loss = loss.detach().clone()
         captured.check()
         if comm is not None and hasattr(comm, "check"):
             comm.check()   # (the peer all-reduce's timeout word)
+        if dump_dir:
+            dumped = step_outputs(loss)
         mode = "hipGraph replay" + (f" ({repeat} steps per replay)" if repeat > 1 else "")
         if sharded:
             what = "peer-write" if args.allreduce == "peer" else "RCCL"
             mode += (f" with the {what} all-reduce captured in the graph" if collective_in_graph
                      else f" split around the host-issued {args.dist_backend} all-reduce")
         floor_ms = None
-        if config == "c2" and not sharded:
+        if args.full and config == "c2" and not sharded:
             # C2's per-eval sum over x_i l_k is reducible to l_k sum_i x_i:
             # the same step with the site kernel's closed form, reported beside the per-eval number
             os.environ["MININF_AMD_BCAST_SUFFSTAT"] = "1"
             arm(f"{config}: reducible-floor graph")
             try:
                 floor_graph = StepGraph(forward_backward, warmup=2, repeat=repeat)
-                warm_replays(floor_graph, max(1, warmup // repeat))
+                warm_replays(floor_graph, max(1, warmup // repeat), repeat)
                 floor_s, _ = timed(floor_graph, steps // repeat)
                 floor_graph.check()
                 floor_ms = 1e3 * floor_s / steps
             finally:
                 del os.environ["MININF_AMD_BCAST_SUFFSTAT"]
-        if not sharded or collective_in_graph:
+        if not args.full:
+            pass   # (the roofline's kernel timing takes runs of its own)
+        elif not sharded or collective_in_graph:
             replay_samples = kernel_timed_replays(repeat)
             kernel_source = (f"graph replays (span stamps: first workgroup start to last "
                              f"workgroup end on the device clock, in a capture of the same step, "
@@ -737,47 +802,49 @@ def run_config(config, args, world, rank, device, group, steps, warmup, cpu_budg
         dist.all_reduce(t)
         evals_all = float(t)
     value = evals_all * steps / elapsed
-    if args.graph and (not sharded or collective_in_graph):
-        times = [t for n, _, t in replay_samples if n == w["dominant_N"]]
-        kernel_ms = sum(times) / len(times) if times else float("nan")
-        launches = len(times)
-    else:
-        kernel_ms, launches = timer.mean_ms(w["dominant_N"])
-    kernel_s = kernel_ms * 1e-3
-    if w["bound"] in ("valu", "mfma"):
-        # FP32 VALU (v_pk_fma_f32) and FP32 MFMA (v_mfma_f32_32x32x2_f32) share the 157.3 TFLOP/s
-        # dense peak on MI355X (MI355X_MICROARCH.md)
-        flops = w["flops_per_eval"] * w["k_local"] * w["n"]
-        achieved = flops / kernel_s / 1e12
-        roof = {"bound": w["bound"], "achieved": achieved, "peak": PEAK_FP32_TFLOPS,
-                "unit": "TFLOP/s", "frac": achieved / PEAK_FP32_TFLOPS, "traffic": None,
-                "kernel": w["kernel"], "kernel_ms": kernel_ms, "launches_timed": launches,
-                "kernel_timing": kernel_source,
-                "algorithmic_per_launch": f"{flops:.4g} FLOP ({w['flop_note']})"}
-    else:
-        nbytes = w["bytes_per_launch"]
-        achieved = nbytes / kernel_s / 1e9
-        roof = {"bound": "hbm", "achieved": achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                "frac": achieved / PEAK_HBM_GBS, "traffic": None, "kernel": w["kernel"],
-                "kernel_ms": kernel_ms, "launches_timed": launches,
-                "kernel_timing": kernel_source,
-                "algorithmic_per_launch": f"{nbytes:.4g} B"}
-    if config == "c5":
-        # the FLOP count prices transcendentals at 1 and omits the Philox integer work, so it is
-        # not the issue-bound resource: the issue model's busy fraction is the bound's fraction
-        busy, busy_source = measured_issue(config)
-        if busy is not None:
-            roof["valu_busy"] = busy
-            roof["valu_busy_source"] = (f"{busy_source} (rocprofv3 --pmc SQ_INSTS_VALU by type x "
-                                        "measured issue cycles / kernel SIMD cycles)")
-    if config == "c4":
-        roof["kernel_timing"] += ("; the stamps span first workgroup start to last workgroup end "
-                                  "and exclude the dispatch (rocprofv3's trace includes it: "
-                                  "~2 us more for this ~24 us launch)")
-    traffic, source = measured_traffic(config)
-    roof["traffic"] = traffic
-    if traffic is not None:
-        roof["traffic_source"] = f"{source} (rocprofv3 --pmc, bytes per launch)"
+    roof = None
+    if args.full:   # the dominant kernel's roofline, from the kernel-timed runs above
+        if args.graph and (not sharded or collective_in_graph):
+            times = [t for n, _, t in replay_samples if n == w["dominant_N"]]
+            kernel_ms = sum(times) / len(times) if times else float("nan")
+            launches = len(times)
+        else:
+            kernel_ms, launches = timer.mean_ms(w["dominant_N"])
+        kernel_s = kernel_ms * 1e-3
+        if w["bound"] in ("valu", "mfma"):
+            # FP32 VALU (v_pk_fma_f32) and FP32 MFMA (v_mfma_f32_32x32x2_f32) share the MI355X's
+            # dense peak of 157.3 TFLOP/s
+            flops = w["flops_per_eval"] * w["k_local"] * w["n"]
+            achieved = flops / kernel_s / 1e12
+            roof = {"bound": w["bound"], "achieved": achieved, "peak": PEAK_FP32_TFLOPS,
+                    "unit": "TFLOP/s", "frac": achieved / PEAK_FP32_TFLOPS, "traffic": None,
+                    "kernel": w["kernel"], "kernel_ms": kernel_ms, "launches_timed": launches,
+                    "kernel_timing": kernel_source,
+                    "algorithmic_per_launch": f"{flops:.4g} FLOP ({w['flop_note']})"}
+        else:
+            nbytes = w["bytes_per_launch"]
+            achieved = nbytes / kernel_s / 1e9
+            roof = {"bound": "hbm", "achieved": achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                    "frac": achieved / PEAK_HBM_GBS, "traffic": None, "kernel": w["kernel"],
+                    "kernel_ms": kernel_ms, "launches_timed": launches,
+                    "kernel_timing": kernel_source,
+                    "algorithmic_per_launch": f"{nbytes:.4g} B"}
+        if config == "c5":
+            # the FLOP count prices transcendentals at 1 and omits the Philox integer work, so it is
+            # not the issue-bound resource: the issue model's busy fraction is the bound's fraction
+            busy, busy_source = measured_issue(config)
+            if busy is not None:
+                roof["valu_busy"] = busy
+                roof["valu_busy_source"] = (f"{busy_source} (rocprofv3 --pmc SQ_INSTS_VALU by "
+                                            "type x measured issue cycles / kernel SIMD cycles)")
+        if config == "c4":
+            roof["kernel_timing"] += ("; the stamps span first workgroup start to last workgroup "
+                                      "end and exclude the dispatch (rocprofv3's trace includes "
+                                      "it: ~2 us more for this ~24 us launch)")
+        traffic, source = measured_traffic(config)
+        roof["traffic"] = traffic
+        if traffic is not None:
+            roof["traffic_source"] = f"{source} (rocprofv3 --pmc, bytes per launch)"
     out = {
         "metric": METRIC, "value": value, "unit": UNIT, "n_gpus": world, "steps": steps,
         "warmup": warmup, "ms_per_step": ms, "higher_is_better": True, "scaling": "weak",
@@ -791,9 +858,10 @@ def run_config(config, args, world, rank, device, group, steps, warmup, cpu_budg
                         " + RCCL grad all-reduce" if args.dist_backend == "nccl" else
                         f" + {args.dist_backend} grad all-reduce") if sharded else ""),
                    "validate": not args.no_validate, "final_loss": float(loss.detach()),
-                   "step_mode": mode, "eager_ms_per_step": eager_ms,
-                   "fusions": loss_fn.last_fusions,
-                   "eager_gc_ms_per_step": gc_clock.seconds * 1e3 / eager_steps,
+                   "step_mode": mode, "fusions": loss_fn.last_fusions,
+                   **({"eager_ms_per_step": eager_ms,
+                       "eager_gc_ms_per_step": gc_clock.seconds * 1e3 / eager_steps}
+                      if eager_ms is not None else {}),
                    **({"reducible_floor_ms_per_step": floor_ms,
                        "reducible_floor_note": "the same step with the site kernel evaluating "
                        "sum_i x_i l_k as l_k sum_i x_i (MININF_AMD_BCAST_SUFFSTAT=1); value and "
@@ -801,8 +869,11 @@ def run_config(config, args, world, rank, device, group, steps, warmup, cpu_budg
                       else {}),
                    "optimizer": ("mininf_amd.optim.Adam (one HIP launch)" if args.optimizer == "mi"
                                  else "torch.optim.Adam(fused=True)")},
-        "roofline": roof,
     }
+    if roof is not None:
+        out["roofline"] = roof
+    if dumped is not None and rank == 0:
+        dump_outputs(dump_dir, dumped)
     out["config"]["ranks"] = world
     out["scaling"] = "weak" if shard is None else "strong"
     if WATCHDOG is not None:
@@ -820,14 +891,25 @@ def main():
     ap.add_argument("--steps", type=int, default=240)
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--warm-ms", type=float, default=50.0,
-                    help="graph warm-up: replay until the device has run this long (ms)")
+                    help="graph warm-up: replay until the device has run this long (ms); with "
+                         "--dump-outputs a fixed number of steps instead (0: none either way)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, measure everything else the line can carry, in "
+                         "runs of their own: timed eager steps, the dominant kernel's roofline, "
+                         "C2's reducible floor, the CPU baseline and (default C2 run) the other "
+                         "configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (loss, "
+                         "guide parameters, their gradients) as DIR/<name>.npy, at most 64 MB in "
+                         "all; the same arguments give the same inputs and step counts")
     ap.add_argument("--config", default="c2")
     ap.add_argument("--no-validate", action="store_true")
     ap.add_argument("--eager", dest="graph", action="store_false",
                     help="launch every step from Python instead of replaying a captured hipGraph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: skip the CPU baseline")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default C2 run: skip measuring C3 / C4 / C5 after it")
+                    help="--full, default C2 run: skip measuring C3 / C4 / C5 after it")
     ap.add_argument("--dist-backend", default="nccl",
                     help="torch.distributed backend for N > 1 (nccl = RCCL over xGMI; gloo lets "
                          "several ranks share one GPU to exercise the sharded path)")
@@ -900,10 +982,11 @@ def main():
             dist.init_process_group(args.dist_backend, **init)
         group = dist.group.WORLD
 
+    cpu_baseline_wanted = args.full and not args.no_cpu_baseline
     out = run_config(args.config, args, world, rank, device, group, args.steps, args.warmup,
-                     0.0 if args.no_cpu_baseline else 12.0)
+                     12.0 if cpu_baseline_wanted else 0.0, dump_dir=args.dump_outputs)
     others = ()
-    if args.config == "c2" and not args.no_other_configs:
+    if args.full and args.config == "c2" and not args.no_other_configs:
         # the other configurations of BASELINE.json, measured in the same run (the same number
         # of graph-replayed steps -- with 10 the fixed cost of the timed region's barriers and
         # synchronisations added 5-9 us to C4's 40 us step; CPU baseline only for C3 at
@@ -915,7 +998,7 @@ def main():
         out["other_configs"] = {}
         for name in others:
             sub = run_config(name, args, world, rank, device, group, args.steps, 3,
-                             0.0 if (args.no_cpu_baseline or name != "c3") else 8.0)
+                             8.0 if (cpu_baseline_wanted and name == "c3") else 0.0)
             out["other_configs"][name] = {key: sub[key] for key in (
                 "value", "unit", "ms_per_step", "scaling", "config", "roofline", "cpu_baseline")
                 if key in sub}

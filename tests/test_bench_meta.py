@@ -24,6 +24,34 @@ def test_measured_traffic_reads_the_pmc_summary():
     assert bench.measured_traffic("c1") == (None, None)
 
 
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): float32 files (float64 kept), and an array over its
+    share of the limit is cut to the same sorted sample of its elements on every call."""
+    import numpy as np
+    import torch
+    bench = load_bench()
+    big = torch.arange(1000, dtype=torch.float32).reshape(10, 100)
+    tensors = {"loss": torch.tensor(1.5, dtype=torch.float64), "param.w": big,
+               "grad.w": big.to(torch.bfloat16), "count": torch.tensor([3, 4])}
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4 * 4 * 100)   # a share of 100 float32 each
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), tensors)
+    assert sorted(os.listdir(tmp_path / "a")) == ["count.npy", "grad.w.npy", "loss.npy",
+                                                  "param.w.npy"]
+    a = {name: np.load(tmp_path / "a" / (name + ".npy")) for name in tensors}
+    assert a["loss"].dtype == np.float64 and a["loss"] == 1.5
+    assert a["count"].dtype == np.float32 and a["count"].tolist() == [3.0, 4.0]
+    assert a["grad.w"].dtype == np.float32
+    sample = a["param.w"]
+    assert sample.dtype == np.float32 and sample.shape == (100,)
+    # the values are their own flat indices: a strictly increasing subset of 0..999
+    assert np.all(np.diff(sample) > 0) and sample.min() >= 0 and sample.max() <= 999
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) \
+        <= 4 * 4 * 100 + 4 * 128
+    for name in tensors:
+        assert np.array_equal(a[name], np.load(tmp_path / "b" / (name + ".npy"))), name
+
+
 def _bench(*argv, env_extra=None):
     import subprocess
     import sys

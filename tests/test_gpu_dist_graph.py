@@ -76,10 +76,11 @@ def test_bench_two_gloo_ranks_match_one_rank_c5_data_sharded(device):
 
 
 def test_bench_n2_default_run_measures_c4_and_c5(device):
-    """`bench.py --gpus 2` (default C2 line) also measures C4 and C5 under other_configs, each
-    entry carrying its rank count and layout."""
+    """`bench.py --gpus 2 --full` (default C2 line) also measures C4 and C5 under other_configs,
+    each entry carrying its rank count and layout."""
     line = _last_json(_bench("--gpus", "2", "--dist-backend", "gloo", "--steps", "4", "--warmup",
-                             "2", "--graph-repeat", "1", "--warm-ms", "0", "--no-cpu-baseline"))
+                             "2", "--graph-repeat", "1", "--warm-ms", "0", "--no-cpu-baseline",
+                             "--full"))
     assert line["n_gpus"] == 2 and line["config"]["ranks"] == 2
     others = line["other_configs"]
     assert sorted(others) == ["c4", "c5"]
