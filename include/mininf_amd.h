@@ -31,6 +31,9 @@
 extern "C" {
 #endif
 
+/* 18 also covers the particle-summed site values (MI_GROUP_KSUM, mi_reduce.ksum / nksum), which
+ * grew mi_reduce and so mi_elbo: a caller built against the earlier 18 is told apart by
+ * mi_elbo_struct_sizes (sizeof(mi_elbo)), which bindings must check beside this number. */
 #define MI_ABI_VERSION 18
 
 #define MI_MAX_SITES 4
@@ -69,6 +72,16 @@ enum mi_grad_mode {
  * workspace (mi_group_draw_partials) instead of reducing them into draw.dloc / draw.dscale -- the
  * ELBO backward reduces them (MI_DRAW_PARTIALS). */
 #define MI_GROUP_DRAW_PARTIALS 2
+/* mi_group.options: leave the site values summed over the particles (mi_reduce.ksum) instead of
+ * one partial per (segment, particle). Honoured by the Bernoulli BCAST kernel over unmasked
+ * contiguous data (k_site_bcast_smem) with at most MI_REDUCE_MAX_SEG segments and K <=
+ * MI_KSUM_MAX_K, and ignored by every other launch (reduce->ksum says which was taken). The
+ * caller must hand the reduction to mi_elbo_forward: with this option honoured,
+ * mi_group_forward_deferred returns MI_EUNSUPPORTED before launching anything when `reduce` is
+ * NULL or `site_lp` is not (per-particle values do not exist in this form), and the workspace
+ * (mi_group_workspace_bytes) has no [nseg, K] block for the site value. */
+#define MI_GROUP_KSUM 4
+#define MI_KSUM_MAX_K 8192
 
 #define MI_FLAG_SUPPORT 1u  /* a (non-masked) value lies outside the family's support */
 #define MI_FLAG_PARAM 2u    /* a parameter violates its constraint (e.g. scale <= 0) */
@@ -257,12 +270,24 @@ typedef struct mi_reduce {
    * constant times a particle-independent sum, e.g. a Bernoulli site's slot gradient over shared
    * data: w dl_k * sum_i x_i - w dl_k N sigmoid(l_k)) */
   int32_t rank1;
-  int32_t pad0;
+  /* 0, or every site value's bit ((1 << num_sites) - 1; anything else is MI_EINVAL). Bit v: value
+   * v arrives summed over the particles (MI_GROUP_KSUM). It has
+   * no segment block in `part` -- the other values' blocks follow one another without it, value
+   * v's block being number v - popcount(ksum & ((1 << v) - 1)) -- and its sum over segments and
+   * particles is the fixed-order fp64 sum of nksum doubles, one per site workgroup that evaluated
+   * a share. The doubles follow the blocks, [popcount(ksum), nksum] row-major (a value's row: its
+   * rank among the set bits) at byte offset round_up(blocks * nseg * K * sizeof(float), 256) of
+   * `part`, blocks = num_sites + num_slots - popcount(ksum); `part` is 8-byte aligned.
+   * For a job with any bit set, total[k] is NOT written (no per-particle value exists) and
+   * site_lp must be NULL: mi_elbo_forward adds g0 * scale[v] * sum straight into the loss.
+   * mi_reduce_launch returns MI_EUNSUPPORTED for such a job. */
+  int32_t ksum;
   double scale[MI_MAX_SITES];
   double slot_scale;
-  float* total;          /* [K] */
+  float* total;          /* [K] (not written when ksum != 0) */
   double* site_lp;       /* [num_sites, K] or NULL */
   float* slot_grad;      /* [num_slots, K] (num_slots > 0) */
+  int64_t nksum;         /* ksum != 0: doubles per particle-summed value */
 } mi_reduce;
 
 /* mi_group_forward with the finalize handed to the caller through *reduce (see above). When
@@ -275,7 +300,8 @@ int mi_group_forward_deferred(const mi_group* group, void* workspace, size_t wor
                               float* total, double* site_lp, float* slot_grad, uint32_t* flags,
                               void* start_event, void* stop_event, void* stream, mi_reduce* reduce);
 
-/* Run a deferred reduction as its own launch. */
+/* Run a deferred reduction as its own launch (MI_EUNSUPPORTED for a job with particle-summed
+ * values, mi_reduce.ksum: only mi_elbo_forward finishes those). */
 int mi_reduce_launch(const mi_reduce* reduce, void* stream);
 
 /* Where a fused-draw group leaves its partial sums (MI_GROUP_DRAW_PARTIALS): dloc partials are
@@ -776,7 +802,9 @@ int mi_elbo_workspace_bytes(const mi_elbo* elbo, size_t* bytes);
 int mi_elbo_workspace_init(void* workspace, size_t workspace_bytes, void* stream);
 
 /* Writes the scalar loss (fp32, reduced in fp64 in a fixed order). MI_EUNSUPPORTED when num_reduce
- * > 0 and a forward-absorbed Beta factor has no dgrad (see mi_elbo.reduce). */
+ * > 0 and a forward-absorbed Beta factor has no dgrad (see mi_elbo.reduce). A launch too large to
+ * reduce its jobs itself runs them as launches of their own first; of a job with particle-summed
+ * values (mi_reduce.ksum) it runs the slots that way and adds the doubles in its lead blocks. */
 int mi_elbo_forward(const mi_elbo* elbo, void* workspace, size_t workspace_bytes, float* loss,
                     void* stream);
 

@@ -33,6 +33,7 @@ NORMAL, BERNOULLI_LOGITS, BERNOULLI_PROBS, BETA, GAMMA, POISSON, INVERSE_GAMMA =
 GRAD_NONE, GRAD_DENSE, GRAD_PARTICLE = 0, 1, 2
 GROUP_FLAGS_ZEROED = 1
 GROUP_DRAW_PARTIALS = 2
+GROUP_KSUM = 4
 TRANSFORM_NONE, TRANSFORM_EXP = 0, 1
 DRAW_NONE, DRAW_SOURCES, DRAW_PARTIALS = 0, 1, 2
 MAX_SOURCES = 4
@@ -150,9 +151,10 @@ class Reduce(ctypes.Structure):
     _fields_ = [
         ("part", c_vp), ("nseg", c_i64), ("K", c_i64),
         ("num_sites", ctypes.c_int32), ("num_slots", ctypes.c_int32),
-        ("rank1", ctypes.c_int32), ("pad0", ctypes.c_int32),
+        ("rank1", ctypes.c_int32), ("ksum", ctypes.c_int32),
         ("scale", ctypes.c_double * MAX_SITES), ("slot_scale", ctypes.c_double),
         ("total", c_vp), ("site_lp", c_vp), ("slot_grad", c_vp),
+        ("nksum", c_i64),
     ]
 
 
@@ -348,6 +350,12 @@ def lib() -> ctypes.CDLL:
         if version != ABI_VERSION:   # the struct mirrors below would be misread
             raise NativeError(f"{LIB_PATH} has ABI version {version}, this binding expects "
                               f"{ABI_VERSION}; rebuild it (mininf_amd/build.py --force).")
+        # (mi_reduce grew within ABI 18: the layout is checked as well as the number)
+        sizes = [ctypes.c_size_t(), ctypes.c_size_t()]
+        handle.mi_elbo_struct_sizes(ctypes.byref(sizes[0]), ctypes.byref(sizes[1]))
+        if sizes[1].value != ctypes.sizeof(Elbo):
+            raise NativeError(f"{LIB_PATH} lays mi_elbo out in {sizes[1].value} bytes, this binding "
+                              f"in {ctypes.sizeof(Elbo)}; rebuild it (mininf_amd/build.py --force).")
         _LIB = handle
     return _LIB
 

@@ -17,6 +17,7 @@
 #include "beta_grad.hpp"
 #include "adam_math.hpp"
 #include "entropy.hpp"
+#include "internal.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -622,6 +623,14 @@ MI_DEV void lds_tree(double* lds, int n) {
   }
 }
 
+// The doubles of job J's particle-summed values (mi_reduce.ksum): after its value blocks.
+MI_DEV const double* ksum_doubles(const mi_reduce& J) {
+  const int blocks = J.num_sites + J.num_slots - __popc((unsigned)J.ksum);
+  const int64_t bytes = (int64_t)blocks * J.nseg * J.K * (int64_t)sizeof(float);
+  return reinterpret_cast<const double*>(reinterpret_cast<const char*>(J.part) +
+                                         ((bytes + 255) & ~(int64_t)255));
+}
+
 // Writes job J's outputs for one block's particles (local block `local` of the job) and returns
 // g0 * the sum of its (fp32) totals (0 from blocks that do not write totals): the block's share of
 // the loss.
@@ -659,15 +668,28 @@ MI_DEV double reduce_job(const mi_elbo& E, float g0, const mi_reduce& J, int loc
   for (int q = 0; q < kMaxTails; ++q)
     tdg[q] = (q < R.tails && gl == 0) ? *reinterpret_cast<const double2*>(pick(R.tail_dgrad, q) + 2 * kc)
                                       : make_double2(0.0, 0.0);
+  double tks = 0.0;   // this lane's share of the particle-summed values
   for (int v = v0; v < v1; ++v) {
+    // values without a block of their own before v (mi_reduce.ksum)
+    const int before = __popc((unsigned)J.ksum & ((1u << v) - 1u));
+    if ((J.ksum >> v) & 1) {
+      // particle-summed: the value's blocks share its doubles, a strided subset per lane in a
+      // fixed order (the block's share sum adds the lanes); no per-particle total exists
+      const double* __restrict__ q = ksum_doubles(J) + (int64_t)before * J.nksum;
+      const int64_t step = (K + kRedK - 1) / kRedK * kElboThreads;
+      double a = 0.0;
+      for (int64_t i = kb * kElboThreads + threadIdx.x; i < J.nksum; i += step) a += q[i];
+      tks += pick(J.scale, v) * a;
+      continue;
+    }
     // rank-one values (mi_reduce.rank1): the particle-independent u[seg], then f[k] u + e[k]
     const bool r1 = (J.rank1 >> v) & 1;
-    const float* __restrict__ p = J.part + (int64_t)v * J.nseg * K + (r1 ? 0 : kc);
+    const float* __restrict__ p = J.part + (int64_t)(v - before) * J.nseg * K + (r1 ? 0 : kc);
     const int64_t stride = r1 ? 1 : K;
     // the rank-one factors of this lane's particle, fetched with the segments (not after them)
     float r1f = 0.0f, r1e = 0.0f;
     if (r1 && gl == 0) {
-      const float* __restrict__ q = J.part + (int64_t)v * J.nseg * K + J.nseg;
+      const float* __restrict__ q = J.part + (int64_t)(v - before) * J.nseg * K + J.nseg;
       r1f = q[kc];
       r1e = q[K + kc];
     }
@@ -732,12 +754,12 @@ MI_DEV double reduce_job(const mi_elbo& E, float g0, const mi_reduce& J, int loc
     }
   }
   double share = 0.0;
-  if (v0 == 0 && gl == 0 && k < K) {
+  if (v0 == 0 && gl == 0 && k < K && J.ksum == 0) {
     const float tf = (float)t;
     J.total[k] = tf;
     share = (double)tf;
   }
-  return (double)g0 * share;
+  return (double)g0 * (share + tks);
 }
 
 MI_DEV double reduce_block(const mi_elbo& E, const ReducePlan& R, int bid,
@@ -861,8 +883,20 @@ __global__ __launch_bounds__(kElboThreads) void k_elbo_forward(const mi_elbo E,
     if (R.external) {
 #pragma unroll
       for (int a = 0; a < MI_MAX_REDUCE; ++a)
-        if (a < R.num)
-          for (int64_t k = first; k < E.K; k += stride) lp += (double)E.reduce[a].total[k];
+        if (a < R.num) {
+          const mi_reduce& J = E.reduce[a];
+          if (J.ksum == 0) {
+            for (int64_t k = first; k < E.K; k += stride) lp += (double)J.total[k];
+          } else {
+            // particle-summed values have no totals: their doubles, row v scaled by scale[v]
+            const double* __restrict__ q = ksum_doubles(J);
+            for (int v = 0; v < J.num_sites; ++v) {
+              double sum = 0.0;
+              for (int64_t i = first; i < J.nksum; i += stride) sum += q[(int64_t)v * J.nksum + i];
+              lp += pick(J.scale, v) * sum;
+            }
+          }
+        }
     }
     for (int f = 0; f < E.num_factors; ++f) {
       const mi_factor& F = E.factors[f];
@@ -1472,6 +1506,11 @@ bool forward_absorbed(const mi_factor& F) {
 }
 
 bool valid_reduce(const mi_elbo* e, const mi_reduce& r) {
+  // particle-summed values: every site value of the job or none (then no per-particle total exists)
+  if (r.ksum != 0 &&
+      ((reinterpret_cast<uintptr_t>(r.part) & 7) != 0 || r.nksum < 1 || r.site_lp != nullptr ||
+       r.num_sites < 1 || r.num_sites > MI_MAX_SITES || r.ksum != (1 << r.num_sites) - 1))
+    return false;
   return r.part != nullptr && r.total != nullptr && r.K == e->K && r.nseg >= 1 &&
          r.nseg <= MI_REDUCE_MAX_SEG && r.num_sites >= 1 && r.num_sites <= MI_MAX_SITES &&
          r.num_slots >= 0 && (r.num_slots == 0 || r.slot_grad != nullptr);
@@ -1642,7 +1681,10 @@ Layout make_layout(const mi_elbo* e) {
     nred += (int)ceil_div(J.K, L.red.kred[r]) * L.red.vblocks[r];
   }
   L.red.first[L.red.num] = nred;
-  if (nred + L.fwd.lead_blocks > mi::kGroupCounters * mi::kGroupBlocks) {
+  // MININF_AMD_ELBO_EXTERNAL=1 takes the large launch's path at any size (tests)
+  const char* ext = std::getenv("MININF_AMD_ELBO_EXTERNAL");
+  const bool force_external = nred > 0 && ext != nullptr && std::atoi(ext) != 0;
+  if (force_external || nred + L.fwd.lead_blocks > mi::kGroupCounters * mi::kGroupBlocks) {
     // too many blocks for the completion counters: mi_elbo_forward launches the reductions on
     // their own first and the lead blocks add the totals
     L.red.external = 1;
@@ -1874,7 +1916,9 @@ int mi_elbo_forward_adam(const mi_elbo* elbo, void* workspace, size_t workspace_
   auto* work = reinterpret_cast<double*>(static_cast<char*>(workspace) + MI_ELBO_COUNTER_BYTES);
   if (L.red.external)
     for (int r = 0; r < elbo->num_reduce; ++r) {
-      const int rc = mi_reduce_launch(&elbo->reduce[r], stream);
+      // (a particle-summed job: its slots only; the lead blocks add its doubles)
+      const int rc = elbo->reduce[r].ksum != 0 ? mi_reduce_launch_slots(&elbo->reduce[r], stream)
+                                                : mi_reduce_launch(&elbo->reduce[r], stream);
       if (rc != 0) return rc;
     }
   bool has_beta = false;

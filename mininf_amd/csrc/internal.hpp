@@ -16,7 +16,16 @@ size_t mi_finalize_scratch_bytes(int64_t nseg, int64_t K, int nv);
 // rank1: bit v marks value v as stored in mi_reduce's rank-one layout (one-launch path only).
 int mi_launch_finalize(const float* part, int64_t nseg, int64_t K, int num_sites, int num_slots,
                        const double* scale, double slot_scale, float* total, double* site_lp,
-                       float* slot_grad, double* scratch, hipStream_t stream, int rank1 = 0);
+                       float* slot_grad, double* scratch, hipStream_t stream, int rank1 = 0,
+                       int ksum = 0);
+// ksum: bit v marks site value v as particle-summed (mi_reduce.ksum): it has no block in `part`
+// (the later values' blocks move up), is skipped, and `total` is not written.
+
+// The slot values of a job whose site values are particle-summed (mi_reduce.ksum != 0), as their
+// own launch: what mi_elbo_forward runs for such a job when the launch is too large to reduce its
+// jobs itself (its lead blocks then add the job's doubles).
+struct mi_reduce;
+int mi_reduce_launch_slots(const mi_reduce* r, void* stream);
 
 // Timing events around a site kernel (the `start_event` / `stop_event` arguments) are for eager
 // launches only. Round 5 first recorded them under capture with hipEventRecordWithFlags(...,

@@ -243,6 +243,19 @@ MI_DEV float block_sum(float v, float* scratch) {
   return out;
 }
 
+// The same in fp64: lanes of a wave (butterfly), then the waves in order.
+MI_DEV double block_sum(double v, double* scratch) {
+  v = wave_sum(v);
+  const int wave = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) scratch[wave] = v;
+  __syncthreads();
+  double out = 0.0;
+#pragma unroll
+  for (int w = 0; w < kBcastThreads / 64; ++w) out += scratch[w];
+  return out;
+}
+
 // Per-particle constants of a BCAST site, computed once per particle (not once per element chunk):
 //   Bernoulli: l, dl/dparam, softplus(l), sigmoid(l)
 //   Normal:    loc, scale, log(scale) + log sqrt(2 pi)
@@ -588,6 +601,12 @@ MI_DEV void beta_side_block(const mi_side& S, int64_t b) {
 // SUFF (MININF_AMD_BCAST_SUFFSTAT=1, a measurement of the floor, not the default): the
 // per-(particle, element) FMA loop replaced by its closed form l_k * sum_i x_i -- the same value
 // in exact arithmetic (C2's per-eval arithmetic is reducible).
+// ksum (mode bit 2, MI_GROUP_KSUM): the site value leaves the launch summed over the workgroup's
+// particles (mi_reduce.ksum) -- registers, then wave, then LDS, in fp64 and a fixed order -- as one
+// double per workgroup, ksum[c * gy + particle block], and the particle-constant segment as one
+// more from each workgroup that evaluates it, ksum[(chunks + s) * gy + particle block] (s: the
+// particle slot, 0 when chunk 0 takes them all). Lanes past K add exactly zero. No [nseg, K] value
+// block exists then: `part` starts with the slot's block.
 // chunk: elements per chunk, a multiple of 32 and at most kSmemMaxChunk (the host sizes it so that
 // chunks x particle blocks fill the chip's workgroup slots: make_plan).
 constexpr int kSmemMaxChunk = 4096;
@@ -596,12 +615,16 @@ __global__ __launch_bounds__(kBcastThreads) void k_site_bcast_smem(const mi_grou
                                                                    float* __restrict__ part,
                                                                    int64_t nseg, int gy,
                                                                    int mode, int chunk,
-                                                                   uint32_t* __restrict__ flags) {
+                                                                   uint32_t* __restrict__ flags,
+                                                                   double* __restrict__ ksum) {
   __shared__ float scratch[kBcastThreads / 64];
+  __shared__ double dscratch[kBcastThreads / 64];
   kernarg_prefetch<(int)sizeof(mi_group)>();
-  // mode bit 0: rank-one slot layout; bit 1: progress-balanced wave priority (below)
+  // mode bit 0: rank-one slot layout; bit 1: progress-balanced wave priority (below); bit 2:
+  // particle-summed values
   const int rank1 = mode & 1;
   const bool balance = (mode & 2) != 0;
+  const bool ksummed = (mode & 4) != 0;
   const int64_t chunks = nseg - 1;
   const int64_t padded = (chunks + 7) / 8 * 8;
   const int64_t b = blockIdx.x;
@@ -794,14 +817,20 @@ __global__ __launch_bounds__(kBcastThreads) void k_site_bcast_smem(const mi_grou
   const float w = (float)st.scale;
   const int64_t extra = nseg - 1;
   uint32_t fl_prior = 0u;
-  float* slot_part = part + (int64_t)(1 + slot_a) * nseg * K;   // (slot_a >= 0)
+  float* slot_part = part + (int64_t)((ksummed ? 0 : 1) + slot_a) * nseg * K;   // (slot_a >= 0)
   if (rank1 && slot_a >= 0 && kblock == 0 && threadIdx.x == 0) slot_part[c] = s_a;   // u[c]
+  double vsum = 0.0;
 #pragma unroll
   for (int p = 0; p < kSmemP; ++p) {
     const int64_t k = kbase + p * kBcastThreads;
     if (k >= K) continue;
-    part[c * K + k] = (float)acc[p];
+    if (ksummed) vsum += acc[p];
+    else part[c * K + k] = (float)acc[p];
     if (slot_a >= 0 && !rank1) slot_part[c * K + k] = w * (s_a * dl[p]);
+  }
+  if (ksummed) {
+    vsum = block_sum(vsum, dscratch);
+    if (threadIdx.x == 0) ksum[c * gy + kblock] = vsum;
   }
   // The particle-constant segment: particle slot p of every lane by the chunk-p workgroups (chunk 0
   // takes all of them when the grid has fewer chunks than particles per lane), one particle at a
@@ -809,6 +838,7 @@ __global__ __launch_bounds__(kBcastThreads) void k_site_bcast_smem(const mi_grou
   const bool spread = chunks >= kSmemP;
   if (spread ? c < kSmemP : c == 0) {
     const int p0 = spread ? (int)c : 0, p1 = spread ? (int)c + 1 : kSmemP;
+    double csum = 0.0;
 #pragma unroll 1
     for (int p = p0; p < p1; ++p) {
       const int64_t k = kbase + p * kBcastThreads;
@@ -831,7 +861,9 @@ __global__ __launch_bounds__(kBcastThreads) void k_site_bcast_smem(const mi_grou
         prior_d = pe.d[2];
         fl_prior |= (pe.param_bad ? MI_FLAG_PARAM : 0u) | (pe.support_bad ? MI_FLAG_SUPPORT : 0u);
       }
-      part[extra * K + k] = (float)(-n * softplus) + prior_lp;
+      const float cv = (float)(-n * softplus) + prior_lp;
+      if (ksummed) csum += (double)cv;
+      else part[extra * K + k] = cv;
       if (slot_a >= 0) {
         const float e = w * (float)(-n * sig * (double)dlp) + w * prior_d;
         if (rank1) {
@@ -841,6 +873,10 @@ __global__ __launch_bounds__(kBcastThreads) void k_site_bcast_smem(const mi_grou
           slot_part[extra * K + k] = e;
         }
       }
+    }
+    if (ksummed) {   // (the branch is uniform over the workgroup)
+      csum = block_sum(csum, dscratch);
+      if (threadIdx.x == 0) ksum[(chunks + (spread ? c : 0)) * gy + kblock] = csum;
     }
   }
   if (rank1 && slot_a >= 0 && kblock == 0 && threadIdx.x == 0 && c == 0) slot_part[extra] = 0.0f;
@@ -856,7 +892,7 @@ struct FinalizeArgs {
   int32_t num_sites;
   int32_t num_slots;
   int32_t rank1;      // bit v: value v in the rank-one layout (mi_reduce.rank1)
-  int32_t pad0;
+  int32_t ksum;       // bit v: site value v is particle-summed (mi_reduce.ksum): no block, skipped
   double scale[MI_MAX_SITES];  // num_sites <= MI_MAX_SITES
   double slot_scale;  // the group's grad_scale: slot gradients are speculative like dense ones
 };
@@ -921,8 +957,10 @@ __global__ __launch_bounds__(kFinK * kFinG) void k_finalize(const T* __restrict_
   const int v_end = split ? v_begin + 1 : nv;
   for (int v = v_begin; v < v_end; ++v) {
     const bool r1 = (A.rank1 >> v) & 1;
+    if ((A.ksum >> v) & 1) continue;   // (uniform over the block)
+    const int blk = v - __popc((unsigned)A.ksum & ((1u << v) - 1u));
     // rank one: the particle-independent u[seg] (stride 1) instead of the per-particle column
-    const T* p = part + (int64_t)v * nseg * K + (r1 ? 0 : kc);
+    const T* p = part + (int64_t)blk * nseg * K + (r1 ? 0 : kc);
     const int64_t stride = r1 ? 1 : K;
     double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
     int64_t g = gl;
@@ -941,7 +979,7 @@ __global__ __launch_bounds__(kFinK * kFinG) void k_finalize(const T* __restrict_
 #pragma unroll
       for (int j = 0; j < kFinG; ++j) acc += red[j][kl];
       if (r1) {
-        const T* q = part + (int64_t)v * nseg * K + nseg;
+        const T* q = part + (int64_t)blk * nseg * K + nseg;
         acc = (double)q[kc] * acc + (double)q[K + kc];
       }
       if (v < A.num_sites) {
@@ -953,7 +991,7 @@ __global__ __launch_bounds__(kFinK * kFinG) void k_finalize(const T* __restrict_
       }
     }
   }
-  if (gl == 0 && k < K && v_begin == 0) total[k] = (float)t;
+  if (gl == 0 && k < K && v_begin == 0 && A.ksum == 0) total[k] = (float)t;
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1272,9 +1310,33 @@ PlanInfo plan_info(const Plan& p, bool combined) {
   return info;
 }
 
-size_t partial_bytes(const mi_group* g, const Plan& p) {
-  const int nv = g->num_sites + g->num_slots;
+// Particle-summed site values (MI_GROUP_KSUM): a k_site_bcast_smem launch whose reduction the
+// ELBO forward can take (a deferrable segment list) over at most MI_KSUM_MAX_K particles (the
+// forward then reduces such a job in a few hundred blocks at most).
+bool use_ksum(const mi_group* g, const Plan& p) {
+  return (g->options & MI_GROUP_KSUM) && p.shape == kBcast && bcast_smem(g) &&
+         p.nseg <= MI_REDUCE_MAX_SEG && g->K >= 4 && g->K <= MI_KSUM_MAX_K;
+}
+
+// The doubles such a launch writes: one per (chunk, particle block), then one per workgroup that
+// evaluates the particle-constant segment (k_site_bcast_smem).
+int64_t ksum_doubles(const Plan& p) {
+  const int64_t chunks = p.nseg - 1;
+  return (chunks + (chunks >= kSmemP ? kSmemP : 1)) * (int64_t)p.grid.y;
+}
+
+// The [nseg, K] fp32 blocks of the values (without the site value's when it is particle-summed).
+size_t slab_bytes(const mi_group* g, const Plan& p) {
+  const int nv = g->num_sites + g->num_slots - (use_ksum(g, p) ? 1 : 0);
   return (size_t)nv * (size_t)p.nseg * (size_t)g->K * sizeof(float);
+}
+
+// Particle-summed values: the doubles follow the (256-byte aligned) blocks.
+size_t ksum_offset(const mi_group* g, const Plan& p) { return (slab_bytes(g, p) + 255) / 256 * 256; }
+
+size_t partial_bytes(const mi_group* g, const Plan& p) {
+  if (!use_ksum(g, p)) return slab_bytes(g, p);
+  return ksum_offset(g, p) + (size_t)ksum_doubles(p) * sizeof(double);
 }
 
 // BCAST groups also hold the per-particle constants after the (256-byte aligned) partials.
@@ -1303,7 +1365,8 @@ bool smem_rank1(const mi_group* g, const Plan& p) {
 }
 
 template <int FAM>
-void launch_smem(const mi_group& G, const Plan& p, float* part, uint32_t* flags, hipStream_t s) {
+void launch_smem(const mi_group& G, const Plan& p, float* part, uint32_t* flags, hipStream_t s,
+                 double* ksum) {
   const dim3 block(mi::kBcastThreads);
   // p.grid = (chunks + side blocks, particle blocks): the kernel takes them as one XCD-aware
   // dimension (see k_site_bcast_smem)
@@ -1311,15 +1374,16 @@ void launch_smem(const mi_group& G, const Plan& p, float* part, uint32_t* flags,
   const int64_t side = (int64_t)p.grid.x - chunks;
   const int gy = (int)p.grid.y;
   const dim3 grid((unsigned)(ceil_div(chunks, 8) * 8 * gy + side));
-  const int rank1 = (smem_rank1(&G, p) ? 1 : 0) | 2;   // bit 2: progress-balanced priorities
+  // bit 1: progress-balanced priorities; bit 2: particle-summed values
+  const int rank1 = (smem_rank1(&G, p) ? 1 : 0) | 2 | (ksum != nullptr ? 4 : 0);
   // MININF_AMD_BCAST_SUFFSTAT=1: the reducible-floor measurement of bench.py (sum_i x_i l_k as
   // l_k sum_i x_i), never the default
   if (env_int("MININF_AMD_BCAST_SUFFSTAT", 0) != 0)
     hipLaunchKernelGGL((mi::k_site_bcast_smem<FAM, kSmemP, true>), grid, block, 0, s,
-                       G, part, p.nseg, gy, rank1, p.chunk, flags);
+                       G, part, p.nseg, gy, rank1, p.chunk, flags, ksum);
   else
     hipLaunchKernelGGL((mi::k_site_bcast_smem<FAM, kSmemP>), grid, block, 0, s, G,
-                       part, p.nseg, gy, rank1, p.chunk, flags);
+                       part, p.nseg, gy, rank1, p.chunk, flags, ksum);
 }
 
 size_t workspace_bytes(const mi_group* g, const Plan& p) {
@@ -1338,18 +1402,20 @@ size_t mi_finalize_scratch_bytes(int64_t nseg, int64_t K, int nv) {
 
 int mi_launch_finalize(const float* part, int64_t nseg, int64_t K, int num_sites, int num_slots,
                        const double* scale, double slot_scale, float* total, double* site_lp,
-                       float* slot_grad, double* scratch, hipStream_t stream, int rank1) {
+                       float* slot_grad, double* scratch, hipStream_t stream, int rank1,
+                       int ksum) {
   if (num_sites > MI_MAX_SITES) return MI_EINVAL;
   mi::FinalizeArgs A{};
   A.num_sites = num_sites;
   A.num_slots = num_slots;
   A.rank1 = rank1;
+  A.ksum = ksum;
   A.slot_scale = slot_scale;
   for (int i = 0; i < num_sites; ++i) A.scale[i] = scale[i];
   const int nv = num_sites + num_slots;
   const unsigned gx = (unsigned)ceil_div(K, mi::kFinK);
   const unsigned gy = num_sites == 1 ? (unsigned)nv : 1u;
-  if (scratch != nullptr && mi_finalize_scratch_bytes(nseg, K, nv) != 0 && rank1 == 0) {
+  if (scratch != nullptr && mi_finalize_scratch_bytes(nseg, K, nv) != 0 && rank1 == 0 && ksum == 0) {
     // long segment lists: chunks of segments in parallel, then the chunk sums
     const int64_t nchunk = ceil_div(nseg, mi::kFinChunk);
     hipLaunchKernelGGL(mi::k_finalize_chunks, dim3(gx, (unsigned)nv, (unsigned)nchunk),
@@ -1361,6 +1427,17 @@ int mi_launch_finalize(const float* part, int64_t nseg, int64_t K, int num_sites
                        stream, part, nseg, K, A, total, site_lp, slot_grad);
   }
   return to_code(hipGetLastError());
+}
+
+int mi_reduce_launch_slots(const mi_reduce* r, void* stream) {
+  if (r == nullptr || r->part == nullptr || r->nseg < 1 || r->K < 1 || r->ksum == 0 ||
+      r->num_sites < 1 || r->num_sites > MI_MAX_SITES || r->num_slots < 0 ||
+      (r->num_slots > 0 && r->slot_grad == nullptr) || r->nseg > MI_REDUCE_MAX_SEG)
+    return MI_EINVAL;
+  if (r->num_slots == 0) return 0;
+  return mi_launch_finalize(r->part, r->nseg, r->K, r->num_sites, r->num_slots, r->scale,
+                            r->slot_scale, r->total, nullptr, r->slot_grad, nullptr,
+                            static_cast<hipStream_t>(stream), r->rank1, r->ksum);
 }
 
 extern "C" {
@@ -1450,6 +1527,13 @@ int mi_group_forward_deferred(const mi_group* group, void* workspace, size_t wor
   }
   const Plan p = make_plan(group);
   if (workspace_bytes < ::workspace_bytes(group, p) || workspace == nullptr) return MI_EWORKSPACE;
+  // particle-summed values exist only for a caller that takes the reduction and wants no
+  // per-particle site values (nothing is enqueued: the caller may launch again without the option)
+  const bool ksummed = use_ksum(group, p);
+  if (ksummed && (reduce == nullptr || site_lp != nullptr)) return MI_EUNSUPPORTED;
+  double* ksum = ksummed ? reinterpret_cast<double*>(static_cast<char*>(workspace) +
+                                                     ksum_offset(group, p))
+                         : nullptr;
   hipStream_t s = static_cast<hipStream_t>(stream);
   float* part = static_cast<float*>(workspace);
   hipError_t e = hipSuccess;
@@ -1508,9 +1592,9 @@ int mi_group_forward_deferred(const mi_group* group, void* workspace, size_t wor
       const bool masked = G.sites[0].mask != nullptr;
       if (smem) {
         if (G.sites[0].family == MI_BERNOULLI_PROBS)
-          launch_smem<MI_BERNOULLI_PROBS>(G, p, part, flags, s);
+          launch_smem<MI_BERNOULLI_PROBS>(G, p, part, flags, s, ksum);
         else
-          launch_smem<MI_BERNOULLI_LOGITS>(G, p, part, flags, s);
+          launch_smem<MI_BERNOULLI_LOGITS>(G, p, part, flags, s, ksum);
         break;
       }
       switch (G.sites[0].family) {
@@ -1584,6 +1668,10 @@ int mi_group_forward_deferred(const mi_group* group, void* workspace, size_t wor
   // values in the rank-one layout: the slot of a k_site_bcast_smem launch (after the site value)
   const int rank1_mask = (smem && smem_rank1(group, p)) ? (1 << reduced_lp) : 0;
   if (reduce != nullptr && prows <= MI_REDUCE_MAX_SEG) {   // the caller runs the finalize
+    if (ksummed) {   // (the smem kernel's one site value)
+      reduce->ksum = 1;   // (its doubles at ksum_offset: mi_reduce.ksum's convention)
+      reduce->nksum = ksum_doubles(p);
+    }
     reduce->part = part;
     reduce->nseg = prows;
     reduce->K = G.K;
@@ -1609,6 +1697,8 @@ int mi_reduce_launch(const mi_reduce* r, void* stream) {
       r->num_sites < 1 || r->num_sites > MI_MAX_SITES || r->num_slots < 0 ||
       (r->num_slots > 0 && r->slot_grad == nullptr) || r->nseg > MI_REDUCE_MAX_SEG)
     return MI_EINVAL;
+  // particle-summed values have no [nseg, K] block to finalize (mi_reduce.ksum)
+  if (r->ksum != 0) return MI_EUNSUPPORTED;
   // nseg <= MI_REDUCE_MAX_SEG: the one-launch finalize (no chunk scratch)
   return mi_launch_finalize(r->part, r->nseg, r->K, r->num_sites, r->num_slots, r->scale,
                             r->slot_scale, r->total, r->site_lp, r->slot_grad, nullptr,

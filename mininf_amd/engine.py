@@ -403,12 +403,14 @@ class _GroupLauncher:
         return log.value.decode()
 
     def run(self, compute_grads: bool, flags: Optional[torch.Tensor] = None,
-            defer: bool = False):
+            defer: bool = False, ksum: bool = False):
         """
         Launch the group. ``flags``: an already-zeroed int32 slice (one word per site) to write the
         validation flags into, e.g. part of one buffer for every group of a step. ``defer``: leave
         the finalize reduction to the caller when the library allows (``self.reduce``, an
-        ``mi_reduce``; None when the launch reduced itself).
+        ``mi_reduce``; None when the launch reduced itself). ``ksum``: the caller hands the
+        reduction to the ELBO forward, so the launch may leave its site values summed over the
+        particles (MI_GROUP_KSUM; ``self.reduce.ksum`` says whether it did).
         """
         device = self.device
         K, N = self.K, self.N
@@ -418,6 +420,8 @@ class _GroupLauncher:
             flags = torch.empty(len(self.flag_sites), dtype=torch.int32, device=device)
         else:
             group.options |= nat.GROUP_FLAGS_ZEROED
+        if ksum and defer and not self.per_site:
+            group.options |= nat.GROUP_KSUM
         if self.prior is not None:   # its word after the group's own
             group.prior.flags = flags.data_ptr() + 4 * len(self.sites)
         size = ctypes.c_size_t()
@@ -1591,6 +1595,8 @@ class _ElboPlan:
         buffers: List[torch.Tensor] = []
         results = []
         deferred: List[Tuple[nat.Reduce, torch.Tensor]] = []   # finalize reductions left to us
+        fuse_env = os.environ.get("MININF_AMD_FUSE_REDUCE", "1") != "0"
+        ksum_env = os.environ.get("MININF_AMD_BCAST_KSUM", "1") != "0"
         # one zeroed flag buffer for every site of the step, in `pending` order (categorical first)
         sizes = [1] * len(self.categorical) + [len(l.flag_sites) for l in self.linears] + \
             [len(l.flag_sites) for l in self.launchers]
@@ -1616,7 +1622,17 @@ class _ElboPlan:
                 job.drawn.base.reshape(self.K, job.drawn.N), job.drawn.conc)
             part = self.flags[cursor:cursor + len(launcher.flag_sites)]
             cursor += len(launcher.flag_sites)
-            total, site_lp, grads, slot_grad, flags = launcher.run(need, part, defer=True)
+            # Particle-summed site values (MI_GROUP_KSUM) only when the reductions will run inside
+            # the ELBO forward -- decided here, before the launch, from what `fused` below is decided
+            # from: the switch, at most MAX_REDUCE launches that can defer, and every absorbed Beta
+            # factor's implicit-gradient factors at hand once this launch has carried its side job
+            # (the launches that honour the option are those that carry one, mi_group_side_supported;
+            # any other ignores it, and asking costs nothing).
+            ksum = ksum_env and fuse_env and not launcher.per_site and \
+                len(self.launchers) + len(self.linears) <= nat.MAX_REDUCE and \
+                len(side_jobs) <= 1 and self._reduce_ok(assume=job)
+            total, site_lp, grads, slot_grad, flags = launcher.run(need, part, defer=True,
+                                                                   ksum=ksum)
             if launcher.reduce is not None:
                 deferred.append((launcher.reduce, total))
             if job is not None and launcher.side_out is not None:
@@ -1681,10 +1697,15 @@ class _ElboPlan:
         # The deferred reductions run inside the ELBO forward (their totals then leave `terms`)
         # unless there are too many, or a forward-absorbed Beta factor lacks its precomputed
         # implicit-gradient factors (mi_elbo.reduce); otherwise each runs as its own launch.
-        fused = self._reduce_ok() and len(deferred) <= nat.MAX_REDUCE and \
-            os.environ.get("MININF_AMD_FUSE_REDUCE", "1") != "0"
+        fused = self._reduce_ok() and len(deferred) <= nat.MAX_REDUCE and fuse_env
         lib = nat.lib()
         self.deferred_count = len(deferred) if fused else 0
+        self.ksum_count = sum(bool(job.ksum) for job, _ in deferred)
+        if self.ksum_count and not fused:
+            # cannot happen: the request above is made from the same facts as `fused` (a
+            # particle-summed job has no per-particle values for mi_reduce_launch; an ELBO launch
+            # too large to reduce its jobs itself handles such a job inside mi_elbo_forward)
+            raise nat.NativeError("particle-summed site values without a fused reduction")
         if fused:
             reduced = {id(t) for _, t in deferred}
             terms = [t for t in terms if id(t) not in reduced]
@@ -1805,19 +1826,21 @@ class _ElboPlan:
             "fused_draws": sum(p.kind == nat.DRAW_PARTIALS for p in self.absorbed.values()),
             "program_draws": sum(l.made_pdraw for l in self.launchers),
             "deferred_reductions": self.deferred_count,
+            "particle_sums": getattr(self, "ksum_count", 0),
             "final_grads": int(getattr(self, "final", None) is not None),
             "optimizer_step": 0,   # set when the optimizer step joins the held launch
         }
 
-    def _reduce_ok(self) -> bool:
+    def _reduce_ok(self, assume=None) -> bool:
         """
         Whether the deferred reductions can join the ELBO forward: every forward-absorbed Beta
         factor has its implicit-gradient factors precomputed (its particle sums then move to the
-        ELBO backward).
+        ELBO backward). ``assume``: a plan whose factors the next site launch computes as its side
+        job.
         """
         for index, plan in self.absorbed.items():
             f = self.factors[index]
-            if f.family != nat.BETA or plan.kind == nat.DRAW_PARTIALS:
+            if f.family != nat.BETA or plan.kind == nat.DRAW_PARTIALS or plan is assume:
                 continue
             dgrad = plan.side_dgrad if plan.side_dgrad is not None else plan.drawn.dgrad
             if dgrad is None:
