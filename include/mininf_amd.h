@@ -393,6 +393,33 @@ int mi_normal_rsample_backward(const float* dz, int64_t dz_stride_k, int64_t dz_
                                void* workspace, size_t workspace_bytes, float* dloc, float* dscale,
                                void* stream);
 
+/* Full-covariance MultivariateNormal guide factor (replaces MultivariateNormal.rsample,
+ * multivariate_normal.py:247-250, over K particles): loc[D], row-major contiguous scale_tril[D, D]
+ * of which only the lower triangle is read, and
+ *   z[k, i] = loc[i] + sum_{j <= i} scale_tril[i, j] * eps[k, j]            (row-major [K, D])
+ * with eps[k, j] exactly the normal mi_normal_rsample / mi_philox_normal produce for (seed,
+ * step (+ *step_device), stream_id, particle_offset + k, element j) with N = D, or read from `eps`
+ * (row-major [K, D]) when it is non-NULL (parity mode). The sum runs over j ascending as one fp32
+ * fma chain starting from loc[i], on v_mfma_f32_32x32x2_f32 for D >= 32: row k of a draw with
+ * particle_offset = o is bit-identical to row k + o of the draw with particle_offset = 0.
+ * 1 <= D <= MI_MVN_MAX_N (larger: MI_EUNSUPPORTED), K >= 1; checked before any device work. */
+int mi_mvn_rsample(const float* loc, const float* scale_tril, int64_t K, int64_t D,
+                   uint64_t seed, uint64_t step, const uint64_t* step_device, uint32_t stream_id,
+                   int64_t particle_offset, const float* eps, float* z, void* stream);
+
+/* Backward of mi_mvn_rsample for upstream dz[k, i] (strided), reduced over particles in a fixed
+ * order (no atomics; particle slices are combined in fp64 through the workspace):
+ *   dloc[i]           = sum_k dz[k, i]
+ *   dscale_tril[i, j] = sum_k dz[k, i] * eps[k, j]   (j <= i), 0 (j > i): all D * D entries written
+ * with eps regenerated from the counter (or read from `eps`); the forward never stores it. */
+int mi_mvn_rsample_backward_workspace_bytes(int64_t K, int64_t D, size_t* bytes);
+int mi_mvn_rsample_backward(const float* dz, int64_t dz_stride_k, int64_t dz_stride_i,
+                            int64_t K, int64_t D, uint64_t seed, uint64_t step,
+                            const uint64_t* step_device, uint32_t stream_id,
+                            int64_t particle_offset, const float* eps,
+                            void* workspace, size_t workspace_bytes,
+                            float* dloc, float* dscale_tril, void* stream);
+
 /* Beta(concentration1, concentration0) draws x[k, i] = G1 / (G1 + G0) with Marsaglia-Tsang gamma
  * variates from the same counter-based generator (beta.py:85-86, dirichlet.py:23-36, 85-88). With
  * `x_in` non-NULL the draws are copied from it instead (parity mode). */

@@ -28,6 +28,7 @@ MAX_FACTORS = 8
 MAX_BUFFERS = 16
 LINEAR_MAX_P = 64
 LINEAR_VALU = 2
+MVN_MAX_N = 1024   # MI_MVN_MAX_N
 
 NORMAL, BERNOULLI_LOGITS, BERNOULLI_PROBS, BETA, GAMMA, POISSON, INVERSE_GAMMA = 0, 1, 2, 3, 4, 5, 6
 GRAD_NONE, GRAD_DENSE, GRAD_PARTICLE = 0, 1, 2
@@ -254,6 +255,13 @@ _SIGNATURES = {
                                                   ctypes.c_uint64, ctypes.c_uint64, c_vp,
                                                   ctypes.c_uint32, c_i64, c_i64, c_vp, c_vp,
                                                   ctypes.c_size_t, c_vp, c_vp, c_vp]),
+    "mi_mvn_rsample": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, ctypes.c_uint64, ctypes.c_uint64,
+                                      c_vp, ctypes.c_uint32, c_i64, c_vp, c_vp, c_vp]),
+    "mi_mvn_rsample_backward_workspace_bytes": (ctypes.c_int, [
+        c_i64, c_i64, ctypes.POINTER(ctypes.c_size_t)]),
+    "mi_mvn_rsample_backward": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, ctypes.c_uint64,
+                                               ctypes.c_uint64, c_vp, ctypes.c_uint32, c_i64,
+                                               c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp, c_vp]),
     "mi_beta_rsample": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, ctypes.c_uint64,
                                        ctypes.c_uint64, c_vp, ctypes.c_uint32, c_i64, c_vp, c_vp,
                                        c_vp]),

@@ -1816,7 +1816,8 @@ class _ElboPlan:
         Normal guide factors drawn per particle by the site program that reads them (mi_group.pdraw,
         no draw launch); deferred_reductions: site
         reductions finished by the ELBO forward; final_grads: the forward wrote the guide
-        gradients (no backward launch for loss.backward()); optimizer_step: the Adam step ran in the held launch's last block (no launch of its own).
+        gradients (no backward launch for loss.backward()); optimizer_step: the Adam step ran in the held launch's last block (no launch of its own);
+        mvn_draws: MultivariateNormal guide factors drawn by the native sampler (mi_mvn_rsample).
         """
         return {
             "folded_priors": sum(l.prior is not None for l in self.launchers) +
@@ -1829,6 +1830,7 @@ class _ElboPlan:
             "particle_sums": getattr(self, "ksum_count", 0),
             "final_grads": int(getattr(self, "final", None) is not None),
             "optimizer_step": 0,   # set when the optimizer step joins the held launch
+            "mvn_draws": guide.mvn_draws(),
         }
 
     def _reduce_ok(self, assume=None) -> bool:
@@ -2238,6 +2240,15 @@ def entropy_factors(approximation) -> Tuple[List[EntropyFactor], list]:
                 fused.append(EntropyFactor(nat.BETA, n, conc, name, factor))
             else:
                 rest.append(factor)
+        elif len(fused) < nat.MAX_FACTORS and guide.native_mvn(factor):
+            # H = sum_i (0.5 + 0.5 log(2 pi) + log L_ii): the Normal entropy of diag(scale_tril),
+            # read at its stride D + 1. The gradient 1 / L_ii comes back as a [D] tensor that
+            # autograd scatters onto the diagonal (DiagonalBackward); the strictly lower entries
+            # receive only the draw's gradient. No distribution is attached: the factor's draw
+            # (mi_mvn_rsample) keeps its own backward, and a gradient routed through a view never
+            # takes the direct-to-leaf paths (nn._accumulate_final_grads declines it).
+            diagonal = factor.scale_tril.diagonal()
+            fused.append(EntropyFactor(nat.NORMAL, int(diagonal.shape[0]), diagonal, name, None))
         else:
             rest.append(factor)
     return fused, rest

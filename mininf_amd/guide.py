@@ -2,14 +2,16 @@
 Reparameterised guide sampling over K particles (replaces ``FactorizedDistribution.rsample``,
 reference ``mininf/nn.py:133-145``, with ONE draw per call at ``nn.py:217``).
 
-Normal, Beta and Gamma factors are drawn by HIP kernels from a counter-based Philox generator keyed
-by (seed, step, factor index, global particle index, element), so that K particles split over W GPUs
-draw exactly the union of what one GPU would draw. Other families (MultivariateNormal, ...) use
-their own ``torch.distributions`` ``rsample`` on the device.
+Normal, Beta, Gamma and full-covariance MultivariateNormal factors are drawn by HIP kernels from a
+counter-based Philox generator keyed by (seed, step, factor index, global particle index, element),
+so that K particles split over W GPUs draw exactly the union of what one GPU would draw. Other
+families (and a batched, float64, host-resident or D > MI_MVN_MAX_N MultivariateNormal) use their
+own ``torch.distributions`` ``rsample`` on the device.
 
-Parity mode: ``noise[name]`` injects host-drawn standard normals (Normal factors, [K, *shape]),
-the draws themselves (Beta factors) or the standard Gamma draws g with x = g / rate (Gamma
-factors), exactly as the oracle's sample-injection protocol does.
+Parity mode: ``noise[name]`` injects host-drawn standard normals (Normal factors, [K, *shape];
+MultivariateNormal factors, [K, D]), the draws themselves (Beta factors) or the standard Gamma
+draws g with x = g / rate (Gamma factors), exactly as the oracle's sample-injection protocol does
+(SURVEY.md 8(c)).
 """
 from __future__ import annotations
 
@@ -19,7 +21,7 @@ import os
 from typing import Dict, Optional, Tuple
 
 import torch
-from torch.distributions import Beta, Distribution, Gamma, Normal
+from torch.distributions import Beta, Distribution, Gamma, MultivariateNormal, Normal
 
 from . import _native as nat
 
@@ -381,6 +383,72 @@ class _GammaRsampleFn(torch.autograd.Function):
         return None, dconc, None, drate, None
 
 
+def native_mvn(distribution) -> bool:
+    """
+    Whether a MultivariateNormal guide factor is drawn by mi_mvn_rsample (and its entropy evaluated
+    by the ELBO kernels): unbatched, float32, on the device, D <= MI_MVN_MAX_N. Any other
+    MultivariateNormal keeps torch's own rsample and entropy.
+    """
+    if type(distribution) is not MultivariateNormal or tuple(distribution.batch_shape) != ():
+        return False
+    loc = distribution.loc
+    return loc.is_cuda and loc.dtype == torch.float32 and \
+        1 <= int(distribution.event_shape[0]) <= nat.MVN_MAX_N
+
+
+class _MvnRsampleFn(torch.autograd.Function):
+    """
+    MultivariateNormal.rsample (multivariate_normal.py:247-250) over K particles:
+    z = loc + eps @ scale_tril^T by mi_mvn_rsample, with the Philox eps of a Normal factor of D
+    elements; the backward regenerates eps (mi_mvn_rsample_backward). ``cfg.noise`` injects eps
+    [K, D], as for a Normal factor.
+    """
+    @staticmethod
+    def forward(ctx, cfg: DrawConfig, loc: torch.Tensor,
+                scale_tril: torch.Tensor):  # type: ignore[override]
+        D, K = loc.shape[0], cfg.K
+        z = torch.empty((K, D), dtype=torch.float32, device=loc.device)
+        seed, step = _philox_key(cfg)
+        nat.check(nat.lib().mi_mvn_rsample(
+            loc.data_ptr(), scale_tril.data_ptr(), K, D, seed, step, nat.ptr(cfg.step_device),
+            cfg.stream_id, cfg.particle_offset, nat.ptr(cfg.noise), z.data_ptr(),
+            nat.stream_handle(loc.device)), "mi_mvn_rsample")
+        ctx.cfg = cfg
+        ctx.D = D
+        return z
+
+    @staticmethod
+    def backward(ctx, dz: torch.Tensor):  # type: ignore[override]
+        cfg: DrawConfig = ctx.cfg
+        D, K = ctx.D, cfg.K
+        device = dz.device
+        if dz.dtype != torch.float32:
+            dz = dz.to(torch.float32)
+        size = ctypes.c_size_t()
+        lib = nat.lib()
+        nat.check(lib.mi_mvn_rsample_backward_workspace_bytes(K, D, ctypes.byref(size)),
+                  "mi_mvn_rsample_backward_workspace_bytes")
+        workspace = torch.empty(max(1, size.value), dtype=torch.uint8, device=device)
+        dloc = torch.empty(D, dtype=torch.float32, device=device)
+        dtril = torch.empty((D, D), dtype=torch.float32, device=device)
+        seed, step = _philox_key(cfg)
+        nat.check(lib.mi_mvn_rsample_backward(
+            dz.data_ptr(), dz.stride(0), dz.stride(1), K, D, seed, step,
+            nat.ptr(backward_step(cfg)), cfg.stream_id, cfg.particle_offset, nat.ptr(cfg.noise),
+            workspace.data_ptr(), size.value, dloc.data_ptr(), dtril.data_ptr(),
+            nat.stream_handle(device)), "mi_mvn_rsample_backward")
+        return None, dloc, dtril
+
+
+# factors the native MultivariateNormal sampler drew in the last draw_all
+# (EvidenceLowerBoundLoss.last_fusions["mvn_draws"])
+_MVN_DRAWS = 0
+
+
+def mvn_draws() -> int:
+    return _MVN_DRAWS
+
+
 # ---- deferred small Normal draws ---------------------------------------------------------------
 # A small Normal factor's [K, N] draw (the regression's theta, N = P features) is made by the loss's
 # planning instead of when the guide is drawn: when the only kernel that reads it is one linear
@@ -673,6 +741,21 @@ def draw(distribution: Distribution, cfg: DrawConfig, lazy: bool = False) -> tor
                 .contiguous()
         x = _GammaRsampleFn.apply(cfg, conc, conc_s, rate, rate_s)
         return x.reshape((cfg.K,) + tuple(shape))
+    if native_mvn(distribution):
+        # the public properties: scale_tril carries the autograd of a covariance_matrix /
+        # precision_matrix parameterisation
+        global _MVN_DRAWS
+        D = int(distribution.event_shape[0])
+        loc = distribution.loc.reshape(D).contiguous()
+        scale_tril = distribution.scale_tril.reshape(D, D)
+        if scale_tril.dtype != torch.float32:
+            raise nat.NativeError(f"guide parameters must be float32, got {scale_tril.dtype}")
+        scale_tril = scale_tril.contiguous()
+        if cfg.noise is not None:   # injected eps, [K, D]
+            cfg.noise = cfg.noise.to(device=loc.device, dtype=torch.float32).reshape(cfg.K, D) \
+                .contiguous()
+        _MVN_DRAWS += 1
+        return _MvnRsampleFn.apply(cfg, loc, scale_tril)
     if cfg.noise is not None:
         return cfg.noise
     return distribution.rsample(torch.Size([cfg.K]))
@@ -689,8 +772,10 @@ def draw_all(approximation: Dict[str, Distribution], K: int, seed: int, step: in
     Normal factors become :class:`LazyDraw` placeholders evaluated inside the site kernels.
     ``element_offsets``: global index of element 0 of data-sharded factors (multiples of 4).
     """
+    global _MVN_DRAWS
     _LAZY.clear()
     _DRAWN.clear()
+    _MVN_DRAWS = 0
     flush_draws(claimed=True)
     samples = {}
     for stream_id, (name, factor) in enumerate(approximation.items()):

@@ -429,6 +429,14 @@ class EvidenceLowerBoundLoss(nn.Module):
             called with are the rank's slice. Shared factors and sites count 1/W per rank, the
             sharded factors draw their slice of the global draw.
 
+    Guide factors of type Normal, Beta, Gamma and MultivariateNormal (unbatched, float32, on the
+    device, at most 1024 dimensions; any of its three parameterisations) are drawn by the native
+    samplers: ``seed`` governs their draws, particle shards draw the union of what one device
+    would draw, and a captured step draws anew on every replay. Their entropy is evaluated inside
+    the ELBO kernels. Every other factor uses its own ``rsample`` (torch's generator) and
+    ``entropy``. ``last_fusions`` reports the fast paths the last evaluation took, among them
+    ``mvn_draws``, the number of factors the native MultivariateNormal sampler drew.
+
     Example:
 
         >>> import torch

@@ -1,0 +1,106 @@
+"""
+The native MultivariateNormal guide factor, as far as a CPU-only host can see it: the library
+exports the sampler's three functions with ctypes signatures, their argument checks run before any
+device work, and a MultivariateNormal the native path does not take (host-resident, batched) keeps
+torch's own rsample and entropy.
+"""
+import ctypes
+
+import torch
+from torch.distributions import MultivariateNormal
+
+from mininf_amd import _native as nat, engine, guide
+from mininf_amd.nn import ParameterizedDistribution
+
+SYMBOLS = ("mi_mvn_rsample", "mi_mvn_rsample_backward_workspace_bytes", "mi_mvn_rsample_backward")
+
+
+def test_library_exports_mvn_sampler():
+    lib = nat.lib()
+    for name in SYMBOLS:
+        assert name in nat._SIGNATURES, name
+        assert hasattr(lib, name), name
+        assert list(getattr(lib, name).argtypes) == list(nat._SIGNATURES[name][1])
+    assert len(nat._SIGNATURES["mi_mvn_rsample"][1]) == 12
+    assert len(nat._SIGNATURES["mi_mvn_rsample_backward"][1]) == 16
+    assert nat.MVN_MAX_N == 1024
+
+
+def test_argument_checks_run_before_any_device_work():
+    lib = nat.lib()
+    buf = (ctypes.c_float * 4)()
+    p = ctypes.addressof(buf)
+    size = ctypes.c_size_t(0)
+
+    def forward(K, D, loc=p, tril=p, z=p, stream_id=0):
+        return lib.mi_mvn_rsample(loc, tril, K, D, 0, 0, None, stream_id, 0, None, z, None)
+
+    def backward(K, D, dz=p, dloc=p, dtril=p):
+        return lib.mi_mvn_rsample_backward(dz, 1, 1, K, D, 0, 0, None, 0, 0, None, None, 0, dloc,
+                                           dtril, None)
+
+    for call in (forward, backward):
+        assert call(1, 0) == nat.MI_EINVAL
+        assert call(0, 1) == nat.MI_EINVAL
+        assert call(-3, 2) == nat.MI_EINVAL
+        assert call(1, nat.MVN_MAX_N + 1) == nat.MI_EUNSUPPORTED
+    assert forward(1, 2, loc=None) == nat.MI_EINVAL
+    assert forward(1, 2, tril=None) == nat.MI_EINVAL
+    assert forward(1, 2, z=None) == nat.MI_EINVAL
+    assert forward(1, 2, stream_id=1 << 24) == nat.MI_EINVAL
+    assert backward(1, 2, dz=None) == nat.MI_EINVAL
+    assert backward(1, 2, dloc=None) == nat.MI_EINVAL
+    assert backward(1, 2, dtril=None) == nat.MI_EINVAL
+    ws = lib.mi_mvn_rsample_backward_workspace_bytes
+    assert ws(1, 0, ctypes.byref(size)) == nat.MI_EINVAL
+    assert ws(0, 1, ctypes.byref(size)) == nat.MI_EINVAL
+    assert ws(1, nat.MVN_MAX_N + 1, ctypes.byref(size)) == nat.MI_EUNSUPPORTED
+    assert ws(1, 1, None) == nat.MI_EINVAL
+    # one particle slice needs no workspace; several need [slices, D * D + D] floats
+    assert ws(32, 1024, ctypes.byref(size)) == 0 and size.value == 0
+    assert ws(256, 64, ctypes.byref(size)) == 0
+    assert size.value > 0 and size.value % (4 * (64 * 64 + 64)) == 0
+    assert ws(4096, 3, ctypes.byref(size)) == 0
+    assert size.value > 0 and size.value % (4 * (3 * 3 + 3)) == 0
+    # a backward that needs a workspace and gets none is refused before it launches
+    assert lib.mi_mvn_rsample_backward(p, 1, 1, 256, 64, 0, 0, None, 0, 0, None, None, 0, p, p,
+                                       None) == nat.MI_EWORKSPACE
+
+
+def test_host_and_batched_mvn_keep_the_torch_path():
+    D, K = 3, 5
+    host = MultivariateNormal(torch.zeros(D), scale_tril=torch.eye(D))
+    batched = MultivariateNormal(torch.zeros(2, D), scale_tril=torch.eye(D).expand(2, D, D))
+    double = MultivariateNormal(torch.zeros(D, dtype=torch.float64),
+                                scale_tril=torch.eye(D, dtype=torch.float64))
+    for factor in (host, batched, double):
+        assert not guide.native_mvn(factor)
+    fused, rest = engine.entropy_factors({"a": host, "b": batched, "c": double})
+    assert fused == [] and rest == [host, batched, double]
+    # the draws come from torch's rsample, on the host, through the unchanged fallback
+    torch.manual_seed(3)
+    samples = guide.draw_all({"a": host, "b": batched}, K, seed=1, step=0, particle_offset=0)
+    torch.manual_seed(3)
+    want = {"a": host.rsample(torch.Size([K])), "b": batched.rsample(torch.Size([K]))}
+    assert guide.mvn_draws() == 0
+    for name in want:
+        assert samples[name].device.type == "cpu"
+        assert torch.equal(samples[name], want[name])
+    assert samples["a"].shape == (K, D) and samples["b"].shape == (K, 2, D)
+
+
+def test_host_mvn_guide_evaluates_through_torch():
+    """A host-resident full-rank guide: draws, entropy and their gradients are torch's own."""
+    D, K = 4, 6
+    module = ParameterizedDistribution(MultivariateNormal, loc=torch.zeros(D),
+                                       scale_tril=torch.eye(D) * 0.5)
+    factor = module()
+    assert not guide.native_mvn(factor)
+    fused, rest = engine.entropy_factors({"theta": factor})
+    assert fused == [] and rest == [factor]
+    z = guide.draw(factor, guide.DrawConfig(K=K, seed=1, step=0, stream_id=0, particle_offset=0))
+    assert z.shape == (K, D) and z.grad_fn is not None
+    value = z.square().sum() / K - sum(f.entropy().sum() for f in rest)
+    value.backward()
+    for p in module.distribution_parameters.values():
+        assert p.grad is not None and torch.isfinite(p.grad).all()
