@@ -53,8 +53,20 @@ enum mi_family {
   MI_BETA = 3,              /* roles: concentration1, concentration0, value  beta.py:88-92, dirichlet.py:90-97 */
   MI_GAMMA = 4,             /* roles: concentration, rate, value  torch/distributions/gamma.py:90-99 */
   MI_POISSON = 5,           /* roles: rate, -, value              torch/distributions/poisson.py:60-65 */
-  MI_INVERSE_GAMMA = 6      /* roles: concentration, rate, value  mininf/distributions.py:5-11: Gamma
+  MI_INVERSE_GAMMA = 6,     /* roles: concentration, rate, value  mininf/distributions.py:5-11: Gamma
                                through PowerTransform(-1), transformed_distribution.py:151-170 */
+  MI_EXPONENTIAL = 7,       /* roles: rate, -, value              torch/distributions/exponential.py:73-76 */
+  MI_LAPLACE = 8,           /* roles: loc, scale, value           torch/distributions/laplace.py:88-91 */
+  MI_CAUCHY = 9,            /* roles: loc, scale, value           torch/distributions/cauchy.py:82-89 */
+  MI_HALF_NORMAL = 10,      /* roles: scale, -, value             half_normal.py:69-74: Normal(0, scale) + log 2 */
+  MI_HALF_CAUCHY = 11,      /* roles: scale, -, value             half_cauchy.py:74-82: Cauchy(0, scale) + log 2 */
+  MI_LOG_NORMAL = 12,       /* roles: loc, scale, value           log_normal.py:49-55: Normal through
+                               ExpTransform, transformed_distribution.py:151-170 */
+  MI_STUDENT_T = 13,        /* roles: loc, scale, value; df = mi_site.extra (a constant of the site)
+                               torch/distributions/studentT.py:102-113 */
+  MI_BINOMIAL = 14,         /* roles: total_count, logits, value  torch/distributions/binomial.py:140-158;
+                               no gradient for total_count */
+  MI_NEGATIVE_BINOMIAL = 15 /* roles: total_count, logits, value  negative_binomial.py:130-150 */
 };
 
 /* what to do with d(site total)/d(operand) */
@@ -102,7 +114,8 @@ typedef struct mi_site {
   int32_t family;        /* enum mi_family */
   int32_t operand[3];    /* role -> operand index, or -1 to use constant[role] */
   float constant[3];
-  int32_t pad0;
+  float extra;           /* a family's fourth, constant input: MI_STUDENT_T's df; unused (0) otherwise.
+                            Takes the place of the former padding word: same size and offset */
   const uint8_t* mask;   /* NULL = all observed; else bool bytes, masked-out elements contribute 0 */
   int64_t mask_stride_k;
   int64_t mask_stride_i;

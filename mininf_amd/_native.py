@@ -31,6 +31,8 @@ LINEAR_VALU = 2
 MVN_MAX_N = 1024   # MI_MVN_MAX_N
 
 NORMAL, BERNOULLI_LOGITS, BERNOULLI_PROBS, BETA, GAMMA, POISSON, INVERSE_GAMMA = 0, 1, 2, 3, 4, 5, 6
+EXPONENTIAL, LAPLACE, CAUCHY, HALF_NORMAL, HALF_CAUCHY, LOG_NORMAL = 7, 8, 9, 10, 11, 12
+STUDENT_T, BINOMIAL, NEGATIVE_BINOMIAL = 13, 14, 15
 GRAD_NONE, GRAD_DENSE, GRAD_PARTICLE = 0, 1, 2
 GROUP_FLAGS_ZEROED = 1
 GROUP_DRAW_PARTIALS = 2
@@ -62,7 +64,7 @@ class Operand(ctypes.Structure):
 class Site(ctypes.Structure):
     _fields_ = [
         ("family", ctypes.c_int32), ("operand", ctypes.c_int32 * 3),
-        ("constant", ctypes.c_float * 3), ("pad0", ctypes.c_int32),
+        ("constant", ctypes.c_float * 3), ("extra", ctypes.c_float),   # STUDENT_T: df
         ("mask", c_vp), ("mask_stride_k", c_i64), ("mask_stride_i", c_i64),
         ("scale", ctypes.c_double),
     ]

@@ -440,7 +440,173 @@ MI_DEV void eval_inverse_gamma(float a, float r, float y, Elem& e) {
   e.support_bad = !(y > 0.0f);
 }
 
-MI_DEV void eval_family(int family, float r0, float r1, float r2, Elem& e) {
+constexpr float kLog2 = 0.69314718055994530942f;    // math.log(2), half_normal.py:72
+constexpr float kLogPi = 1.14472988584940017414f;   // math.log(math.pi), cauchy.py:86
+
+// torch.sign as autograd uses it for d|x|/dx: 0 at 0.
+MI_DEV float sign0(float x) { return (x > 0.0f ? 1.0f : 0.0f) - (x < 0.0f ? 1.0f : 0.0f); }
+
+// Exponential(rate): log(rate) - rate v
+// torch/distributions/exponential.py:73-76; support nonnegative (v >= 0), rate > 0.
+MI_DEV void eval_exponential(float rate, float v, Elem& e) {
+  e.lp = logf(rate) - rate * v;
+  e.d[0] = rcp(rate) - v;
+  e.d[1] = 0.0f;
+  e.d[2] = -rate;
+  e.param_bad = !(rate > 0.0f);
+  e.support_bad = !(v >= 0.0f);
+}
+
+// Laplace(loc, scale): -log(2 scale) - |v - loc| / scale
+// torch/distributions/laplace.py:88-91; support real. d|x|/dx = sign(x), 0 at 0 (sign0). With a
+// constant scale, 1 / scale and log(2 scale) are loop invariants.
+MI_DEV void eval_laplace(float loc, float scale, float v, Elem& e) {
+  const float inv = rcp(scale);
+  const float diff = v - loc;
+  const float a = fabsf(diff) * inv;
+  e.lp = -logf(2.0f * scale) - a;
+  const float g = sign0(diff) * inv;
+  e.d[0] = g;
+  e.d[1] = (a - 1.0f) * inv;   // -1 / scale + |diff| / scale^2
+  e.d[2] = -g;
+  e.param_bad = !(scale > 0.0f) || (loc != loc);
+  e.support_bad = (v != v);
+}
+
+// Cauchy(loc, scale): -log(pi) - log(scale) - log1p(y^2), y = (v - loc) / scale
+// torch/distributions/cauchy.py:82-89; support real.
+MI_DEV void eval_cauchy(float loc, float scale, float v, Elem& e) {
+  const float inv = rcp(scale);
+  const float y = (v - loc) * inv;
+  const float q = y * y;
+  e.lp = -(kLogPi + logf(scale)) - log1pf(q);
+  const float r = inv * rcp(1.0f + q);    // 1 / (scale (1 + y^2))
+  const float g = 2.0f * y * r;
+  e.d[0] = g;
+  e.d[1] = (q - 1.0f) * r;                // -1 / scale + 2 y^2 / (scale (1 + y^2))
+  e.d[2] = -g;
+  e.param_bad = !(scale > 0.0f) || (loc != loc);
+  e.support_bad = (v != v);
+}
+
+// HalfNormal(scale): where(v >= 0, Normal(0, scale).log_prob(v) + log 2, -inf)
+// torch/distributions/half_normal.py:69-74; support nonnegative.
+MI_DEV void eval_half_normal(float scale, float v, Elem& e) {
+  Elem n;
+  eval_normal(0.0f, scale, v, n);
+  e.lp = v >= 0.0f ? n.lp + kLog2 : -__builtin_inff();
+  e.d[0] = n.d[1];
+  e.d[1] = 0.0f;
+  e.d[2] = n.d[2];
+  e.param_bad = !(scale > 0.0f);
+  e.support_bad = !(v >= 0.0f);
+}
+
+// HalfCauchy(scale): where(v >= 0, Cauchy(0, scale).log_prob(v) + log 2, -inf)
+// torch/distributions/half_cauchy.py:74-82; support nonnegative.
+MI_DEV void eval_half_cauchy(float scale, float v, Elem& e) {
+  Elem c;
+  eval_cauchy(0.0f, scale, v, c);
+  e.lp = v >= 0.0f ? c.lp + kLog2 : -__builtin_inff();
+  e.d[0] = c.d[1];
+  e.d[1] = 0.0f;
+  e.d[2] = c.d[2];
+  e.param_bad = !(scale > 0.0f);
+  e.support_bad = !(v >= 0.0f);
+}
+
+// LogNormal(loc, scale) = Normal(loc, scale) pushed through y = exp(x) (log_normal.py:49-55):
+// TransformedDistribution.log_prob (transformed_distribution.py:151-170) with x = log(y) and
+// ExpTransform.log_abs_det_jacobian = x (transforms.py):
+//   Normal.log_prob(log y) - log y;  support positive.
+MI_DEV void eval_log_normal(float loc, float scale, float y, Elem& e) {
+  const float x = logf(y);
+  Elem n;
+  eval_normal(loc, scale, x, n);
+  e.lp = n.lp - x;
+  e.d[0] = n.d[0];
+  e.d[1] = n.d[1];
+  e.d[2] = (n.d[2] - 1.0f) * rcp(y);   // dx/dy = 1 / y
+  e.param_bad = n.param_bad;
+  e.support_bad = !(y > 0.0f);
+}
+
+// The part of StudentT's normaliser Z that depends on df alone (studentT.py:106-112):
+//   0.5 log(df) + 0.5 log(pi) + lgamma(df / 2) - lgamma((df + 1) / 2)
+// The two lgamma cancel to a few ulp of their size in fp32, so it is evaluated in fp64. df is a
+// constant of the site (mi_site.extra): the site programs compute this once per thread.
+MI_DEV float student_t_norm(float df) {
+  const double d = (double)df;
+  return (float)(0.5 * log(d) + 0.57236494292470008707 + lgamma(0.5 * d) - lgamma(0.5 * (d + 1.0)));
+}
+
+// StudentT(df, loc, scale): -(df + 1) / 2 log1p(y^2 / df) - log(scale) - norm, y = (v - loc) / scale,
+// norm = student_t_norm(df); torch/distributions/studentT.py:102-113; support real, df > 0.
+// No derivative with respect to df: the native family takes a constant df.
+MI_DEV void eval_student_t(float loc, float scale, float v, float df, float norm, Elem& e) {
+  const float inv = rcp(scale);
+  const float y = (v - loc) * inv;
+  const float q = y * y;
+  e.lp = (-0.5f * (df + 1.0f)) * log1pf(q * rcp(df)) - (logf(scale) + norm);
+  const float r = (df + 1.0f) * inv * rcp(df + q);   // (df + 1) / (scale (df + y^2))
+  const float g = y * r;
+  e.d[0] = g;
+  e.d[1] = fmaf(q, r, -inv);              // -1 / scale + (df + 1) y^2 / (scale (df + y^2))
+  e.d[2] = -g;
+  e.param_bad = !(scale > 0.0f) || !(df > 0.0f) || (loc != loc);
+  e.support_bad = (v != v);
+}
+
+// t = exp(-|l|) and log1p(t): the shared part of softplus(l) = max(l, 0) + log1p(t),
+// logsigmoid(l) = min(l, 0) - log1p(t) and sigmoid(l) = l >= 0 ? 1 / (1 + t) : t / (1 + t).
+MI_DEV float sigmoid_parts(float l, float& log1p_t) {
+  const float t = expf(-fabsf(l));
+  log1p_t = log1pf(t);
+  const float r = rcp(1.0f + t);
+  return l >= 0.0f ? r : t * r;
+}
+
+// Binomial(n, logits l):
+//   v l - lgamma(v + 1) - lgamma(n - v + 1) - (n max(l, 0) + n log1p(exp(-|l|)) - lgamma(n + 1))
+// torch/distributions/binomial.py:140-158 (always through self.logits); support the integers in
+// [0, n], n a nonnegative integer. v l - n max(l, 0) is formed as (v - n) l for l >= 0: the same
+// value without the cancellation of two large products. d/dn = 0 (torch gives total_count no
+// meaningful gradient); d/dv is torch's continuous derivative.
+MI_DEV void eval_binomial(float n, float l, float v, Elem& e) {
+  float l1p;
+  const float sig = sigmoid_parts(l, l1p);
+  const float coef = lgammaf(n + 1.0f) - lgammaf(v + 1.0f) - lgammaf(n - v + 1.0f);
+  e.lp = ((l >= 0.0f ? v - n : v) * l - n * l1p) + coef;
+  e.d[0] = 0.0f;
+  e.d[1] = v - n * sig;
+  e.d[2] = l + (float)(digamma((double)n - (double)v + 1.0) - digamma((double)v + 1.0));
+  e.param_bad = !(n >= 0.0f && n == floorf(n)) || (l != l);
+  e.support_bad = !(v >= 0.0f && v <= n && v == floorf(v));
+}
+
+// NegativeBinomial(r, logits l):
+//   r logsigmoid(-l) + v logsigmoid(l) - (-lgamma(r + v) + lgamma(1 + v) + lgamma(r)),
+// the normalisation masked to 0 where r + v == 0 (probability 1, lgamma(0) infinite);
+// torch/distributions/negative_binomial.py:130-150; support nonnegative integers, r >= 0.
+// d/dv is torch's continuous derivative; the masked normalisation contributes no derivative.
+MI_DEV void eval_negative_binomial(float r, float l, float v, Elem& e) {
+  float l1p;
+  const float sig = sigmoid_parts(l, l1p);
+  const float ls_pos = fminf(l, 0.0f) - l1p;    // logsigmoid(l)
+  const float ls_neg = fminf(-l, 0.0f) - l1p;   // logsigmoid(-l)
+  const bool point = (r + v == 0.0f);
+  const float norm = point ? 0.0f : -lgammaf(r + v) + lgammaf(1.0f + v) + lgammaf(r);
+  e.lp = (r * ls_neg + v * ls_pos) - norm;
+  const double psi_rv = point ? 0.0 : digamma((double)r + (double)v);
+  e.d[0] = ls_neg + (point ? 0.0f : (float)(psi_rv - digamma((double)r)));
+  e.d[1] = v - (v + r) * sig;
+  e.d[2] = ls_pos + (point ? 0.0f : (float)(psi_rv - digamma((double)v + 1.0)));
+  e.param_bad = !(r >= 0.0f) || (l != l);
+  e.support_bad = !(v >= 0.0f && v == floorf(v));
+}
+
+// `extra`: mi_site.extra (StudentT's df).
+MI_DEV void eval_family(int family, float r0, float r1, float r2, float extra, Elem& e) {
   switch (family) {
     case MI_NORMAL: eval_normal(r0, r1, r2, e); break;
     case MI_BERNOULLI_LOGITS: eval_bernoulli_logits(r0, r2, e); break;
@@ -448,6 +614,15 @@ MI_DEV void eval_family(int family, float r0, float r1, float r2, Elem& e) {
     case MI_GAMMA: eval_gamma(r0, r1, r2, e); break;
     case MI_POISSON: eval_poisson(r0, r2, e); break;
     case MI_INVERSE_GAMMA: eval_inverse_gamma(r0, r1, r2, e); break;
+    case MI_EXPONENTIAL: eval_exponential(r0, r2, e); break;
+    case MI_LAPLACE: eval_laplace(r0, r1, r2, e); break;
+    case MI_CAUCHY: eval_cauchy(r0, r1, r2, e); break;
+    case MI_HALF_NORMAL: eval_half_normal(r0, r2, e); break;
+    case MI_HALF_CAUCHY: eval_half_cauchy(r0, r2, e); break;
+    case MI_LOG_NORMAL: eval_log_normal(r0, r1, r2, e); break;
+    case MI_STUDENT_T: eval_student_t(r0, r1, r2, extra, student_t_norm(extra), e); break;
+    case MI_BINOMIAL: eval_binomial(r0, r1, r2, e); break;
+    case MI_NEGATIVE_BINOMIAL: eval_negative_binomial(r0, r1, r2, e); break;
     default: eval_beta(r0, r1, r2, e); break;
   }
 }

@@ -59,13 +59,23 @@ const char* eval_fn(int family) {
     case MI_GAMMA: return "eval_gamma";
     case MI_POISSON: return "eval_poisson";
     case MI_INVERSE_GAMMA: return "eval_inverse_gamma";
+    case MI_EXPONENTIAL: return "eval_exponential";
+    case MI_LAPLACE: return "eval_laplace";
+    case MI_CAUCHY: return "eval_cauchy";
+    case MI_HALF_NORMAL: return "eval_half_normal";
+    case MI_HALF_CAUCHY: return "eval_half_cauchy";
+    case MI_LOG_NORMAL: return "eval_log_normal";
+    case MI_STUDENT_T: return "eval_student_t";
+    case MI_BINOMIAL: return "eval_binomial";
+    case MI_NEGATIVE_BINOMIAL: return "eval_negative_binomial";
     default: return "eval_beta";
   }
 }
 
 // Families whose density has no second parameter role (their eval_* take (r0, value)).
 bool one_param(int family) {
-  return family == MI_BERNOULLI_LOGITS || family == MI_BERNOULLI_PROBS || family == MI_POISSON;
+  return family == MI_BERNOULLI_LOGITS || family == MI_BERNOULLI_PROBS || family == MI_POISSON ||
+         family == MI_EXPONENTIAL || family == MI_HALF_NORMAL || family == MI_HALF_CAUCHY;
 }
 
 bool role_used(int family, int q) { return !(one_param(family) && q == 1); }
@@ -162,6 +172,9 @@ void emit_site_eval(std::ostringstream& o, const mi_group& g, int s, const std::
   o << in << "{\n" << in << "  mi::Elem el;\n";
   if (one_param(st.family))
     o << in << "  mi::" << eval_fn(st.family) << "(" << r[0] << ", " << r[2] << ", el);\n";
+  else if (st.family == MI_STUDENT_T)   // df (mi_site.extra) and its normaliser: df<s>, tn<s>
+    o << in << "  mi::eval_student_t(" << r[0] << ", " << r[1] << ", " << r[2] << ", df" << s
+      << ", tn" << s << ", el);\n";
   else
     o << in << "  mi::" << eval_fn(st.family) << "(" << r[0] << ", " << r[1] << ", " << r[2]
       << ", el);\n";
@@ -346,6 +359,9 @@ std::string generate(const mi_group& g, const PlanInfo& plan) {
   for (int s = 0; s < g.num_sites; ++s) {
     o << "  bool pb" << s << " = false, sb" << s << " = false;\n";
     o << "  const float scale" << s << " = (float)G.sites[" << s << "].scale;\n";
+    if (g.sites[s].family == MI_STUDENT_T)   // once per thread, outside every loop
+      o << "  const float df" << s << " = G.sites[" << s << "].extra, tn" << s
+        << " = mi::student_t_norm(df" << s << ");\n";
     for (int q = 0; q < 3; ++q)
       if (g.sites[s].operand[q] < 0 && role_used(g.sites[s].family, q))
         o << "  const float c" << s << "_" << q << " = G.sites[" << s << "].constant[" << q << "];\n";

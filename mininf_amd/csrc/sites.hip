@@ -79,7 +79,7 @@ MI_DEV void group_element(const mi_group& G, int64_t k, int64_t i, float (&lp)[M
       bool observed = true;
       if (st.mask != nullptr) observed = st.mask[k * st.mask_stride_k + i * st.mask_stride_i] != 0;
       Elem e;
-      eval_family(st.family, r[0], r[1], r[2], e);
+      eval_family(st.family, r[0], r[1], r[2], st.extra, e);
       lp[s] += observed ? e.lp : 0.0f;
       fl[s] |= (e.param_bad ? MI_FLAG_PARAM : 0u) | ((observed && e.support_bad) ? MI_FLAG_SUPPORT : 0u);
       if (G.compute_grads) {
@@ -1116,7 +1116,7 @@ bool validate_group(const mi_group* g) {
   if (g->num_slots < 0 || g->num_slots > MI_MAX_SLOTS) return false;
   for (int s = 0; s < g->num_sites; ++s) {
     const mi_site& st = g->sites[s];
-    if (st.family < MI_NORMAL || st.family > MI_INVERSE_GAMMA) return false;
+    if (st.family < MI_NORMAL || st.family > MI_NEGATIVE_BINOMIAL) return false;
     if (st.operand[2] < 0) return false;  // the value is always an operand
     for (int q = 0; q < 3; ++q)
       if (st.operand[q] >= g->num_operands) return false;

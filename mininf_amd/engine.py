@@ -47,7 +47,23 @@ FAMILY_CODES = {
     "gamma": nat.GAMMA,
     "poisson": nat.POISSON,
     "inverse_gamma": nat.INVERSE_GAMMA,
+    "exponential": nat.EXPONENTIAL,
+    "laplace": nat.LAPLACE,
+    "cauchy": nat.CAUCHY,
+    "half_normal": nat.HALF_NORMAL,
+    "half_cauchy": nat.HALF_CAUCHY,
+    "log_normal": nat.LOG_NORMAL,
+    "student_t": nat.STUDENT_T,
+    "binomial": nat.BINOMIAL,
+    "negative_binomial": nat.NEGATIVE_BINOMIAL,
 }
+
+# families with one parameter role: (parameter, -, value) in mi_site
+_ONE_PARAMETER = ("bernoulli_logits", "bernoulli_probs", "poisson", "exponential", "half_normal",
+                  "half_cauchy")
+# families over the integers, whose values (and Binomial / NegativeBinomial total_count) may
+# arrive as integer tensors
+_INTEGER_VALUED = ("poisson", "binomial", "negative_binomial")
 
 
 def _collapse(t: torch.Tensor, K: int, shape: torch.Size) -> "_View":
@@ -351,8 +367,8 @@ class _GroupLauncher:
         for index, (site, roles, mask) in enumerate(self.sites):
             desc = group.sites[index]
             desc.family = FAMILY_CODES[site.family]
-            if site.family.startswith("bernoulli") or site.family == "poisson":
-                roles = [roles[0], (-1, 0.0), roles[1]]   # one-parameter families
+            if site.family in _ONE_PARAMETER:
+                roles = [roles[0], (-1, 0.0), roles[1]]
             for q in range(3):
                 desc.operand[q] = roles[q][0]
                 desc.constant[q] = roles[q][1]
@@ -362,6 +378,7 @@ class _GroupLauncher:
                 desc.mask = mask.tensor.data_ptr()
                 desc.mask_stride_k, desc.mask_stride_i = mask.sk, mask.si
             desc.scale = site.scale
+            desc.extra = site.extra
         if self.prior is not None:
             pr = group.prior
             pr.present, pr.family = 1, self.prior[1]
@@ -1071,8 +1088,11 @@ def plan_groups(trace: ParticleTrace, g0: float, device: torch.device):
             if lazy is not None:   # exact-shape use, checked by _lazy_uses
                 views.append(_View(None, N, 1, None, lazy))
                 continue
-            if is_value and site.family == "poisson" and not t.is_floating_point():
-                t = t.to(torch.float32)   # integer counts (exact in fp32 below 2^24)
+            if site.family in _INTEGER_VALUED and not t.is_floating_point() and \
+                    (is_value or (role == 0 and site.family != "poisson")):
+                # integer counts and an integer total_count (exact in fp32 below 2^24); the
+                # converted tensor takes no gradient (MI_GRAD_NONE)
+                t = t.to(torch.float32)
             moved, constant = _to_device(_float(t, site.name), K, device, f"site '{site.name}'",
                                          allow_constant=not is_value)
             views.append(_View(None, 0, 0, constant) if constant is not None

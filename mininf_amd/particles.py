@@ -28,14 +28,16 @@ import weakref
 from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, cast
 
 import torch
-from torch.distributions import Bernoulli, Beta, Categorical, Distribution, Gamma, \
-    MultivariateNormal, Normal, Poisson, PowerTransform, TransformedDistribution
+from torch.distributions import Bernoulli, Beta, Binomial, Categorical, Cauchy, Distribution, \
+    Exponential, ExpTransform, Gamma, HalfCauchy, HalfNormal, Laplace, LogNormal, \
+    MultivariateNormal, NegativeBinomial, Normal, Poisson, PowerTransform, StudentT, \
+    TransformedDistribution
 from torch.distributions.constraints import Constraint
 from torch.distributions.utils import lazy_property
 from torch.overrides import TorchFunctionMode
 from torch.utils._pytree import tree_flatten, tree_map
 
-from . import core, data, mvn, predictive
+from . import core, data, graph, mvn, predictive
 from .distributions import InverseGamma
 from .core import batch, no_log_prob, State, TracerMixin, Value, validate_shape
 from .util import _normalize_shape, check_constraint, OptionalSize
@@ -111,6 +113,7 @@ class SiteRecord:
     linear_theta_index: int = -1
     linear_theta: Optional[torch.Tensor] = None
     order: int = 0   # position of the sample statement in the model (errors raise in this order)
+    extra: float = 0.0   # the family's constant fourth input (mi_site.extra): StudentT's df
 
 
 @dataclasses.dataclass
@@ -292,27 +295,105 @@ def classify(distribution: Distribution) -> Tuple[str, List[Any]]:
     Map a distribution onto a HIP site family and its role tensors, or ``("torch", [])``.
     Exact type checks: subclasses may override ``log_prob``.
     """
+    family, params, _ = _classify(distribution)
+    return family, params
+
+
+def _classify(distribution: Distribution) -> Tuple[str, List[Any], float]:
+    """:func:`classify` plus the family's constant fourth input (``mi_site.extra``: StudentT's df)."""
     cls = type(distribution)
     if cls is Normal:
-        return "normal", [distribution.loc, distribution.scale]
+        return "normal", [distribution.loc, distribution.scale], 0.0
     if cls is Bernoulli:
         # torch evaluates via self.logits (bernoulli.py:121-125); use whichever parameter the
         # distribution was constructed with so no extra lazy tensor is materialised.
         if "logits" in distribution.__dict__:
-            return "bernoulli_logits", [distribution.logits]
-        return "bernoulli_probs", [distribution.probs]
+            return "bernoulli_logits", [distribution.logits], 0.0
+        return "bernoulli_probs", [distribution.probs], 0.0
     if cls is Beta:
-        return "beta", [distribution.concentration1, distribution.concentration0]
+        return "beta", [distribution.concentration1, distribution.concentration0], 0.0
     if cls is Categorical:
-        return "categorical", [distribution.logits]
+        return "categorical", [distribution.logits], 0.0
     if cls is Gamma:
-        return "gamma", [distribution.concentration, distribution.rate]
+        return "gamma", [distribution.concentration, distribution.rate], 0.0
     if cls is Poisson:
-        return "poisson", [distribution.rate]
+        return "poisson", [distribution.rate], 0.0
     if _is_inverse_gamma(distribution):
         base = cast(Gamma, cast(TransformedDistribution, distribution).base_dist)
-        return "inverse_gamma", [base.concentration, base.rate]
-    return "torch", []
+        return "inverse_gamma", [base.concentration, base.rate], 0.0
+    if cls is Exponential:
+        return "exponential", [distribution.rate], 0.0
+    if cls is Laplace:
+        return "laplace", [distribution.loc, distribution.scale], 0.0
+    if cls is Cauchy:
+        return "cauchy", [distribution.loc, distribution.scale], 0.0
+    # HalfNormal / HalfCauchy / LogNormal are TransformedDistributions of a Normal / Cauchy built
+    # by their own constructors (half_normal.py:48-50, half_cauchy.py:47-49, log_normal.py:49-51)
+    if cls is HalfNormal and type(distribution.base_dist) is Normal:
+        return "half_normal", [distribution.base_dist.scale], 0.0
+    if cls is HalfCauchy and type(distribution.base_dist) is Cauchy:
+        return "half_cauchy", [distribution.base_dist.scale], 0.0
+    if _is_log_normal(distribution):
+        base = cast(Normal, cast(TransformedDistribution, distribution).base_dist)
+        return "log_normal", [base.loc, base.scale], 0.0
+    # (a StudentT of three host numbers, e.g. a StudentT(3., 0., 1.) prior, stays a torch site: the
+    # captured-step handling of a torch site's host constants is pinned on it, DESIGN.md 9)
+    if cls is StudentT and not (_host_number(distribution.loc) and
+                                _host_number(distribution.scale)):
+        df = _student_t_df(distribution)
+        if df is not None:
+            return "student_t", [distribution.loc, distribution.scale], df
+    # torch evaluates both through self.logits (binomial.py:140-158, negative_binomial.py:130-150):
+    # for a `probs` construction that is torch's own lazy probs_to_logits, inside the trace, so
+    # its clamp and its autograd stay torch's.
+    if cls is Binomial:
+        return "binomial", [distribution.total_count, distribution.logits], 0.0
+    if cls is NegativeBinomial:
+        return "negative_binomial", [distribution.total_count, distribution.logits], 0.0
+    return "torch", [], 0.0
+
+
+def _is_log_normal(distribution: Distribution) -> bool:
+    """
+    Normal through a single ExpTransform (torch's LogNormal, or the same construction spelled out)
+    whose log_prob is TransformedDistribution's own.
+    """
+    return isinstance(distribution, TransformedDistribution) and \
+        type(distribution).log_prob is TransformedDistribution.log_prob and \
+        type(distribution.base_dist) is Normal and len(distribution.transforms) == 1 and \
+        type(distribution.transforms[0]) is ExpTransform
+
+
+def _host_number(t: Any) -> bool:
+    """A Python number, or what a distribution's constructor makes of one: an unbatched host
+    tensor of one element (possibly broadcast) that does not require grad."""
+    if not isinstance(t, torch.Tensor):
+        return True
+    return not is_batched(t) and t.device.type == "cpu" and not t.requires_grad and \
+        all(stride == 0 for stride, size in zip(t.stride(), t.shape) if size != 1)
+
+
+def _student_t_df(distribution: StudentT) -> Optional[float]:
+    """
+    The df of a StudentT the site kernels evaluate: a constant of the site (``mi_site.extra``), so
+    a Python number or a one-element tensor that neither requires grad nor depends on the particle
+    (StudentT's constructor broadcasts it: a view of one element). None for any other df: the
+    site then takes the torch path.
+    """
+    df = distribution.df
+    if not isinstance(df, torch.Tensor):
+        return float(df)
+    if is_batched(df) or df.requires_grad or df.numel() == 0 or \
+            any(stride != 0 for stride, size in zip(df.stride(), df.shape) if size != 1):
+        return None
+    if df.device.type != "cpu":
+        # the number of a distribution built in a warm-up / captured step (mininf_amd.graph)
+        value = graph.CONSTANT_VALUES.get(df.data_ptr())
+        if value is not None:
+            return value
+        if torch.cuda.is_current_stream_capturing():
+            return None   # unreadable while capturing: the generic torch site path (same density)
+    return float(df.reshape(-1)[0])
 
 
 def _is_inverse_gamma(distribution: Distribution) -> bool:
@@ -414,7 +495,7 @@ class ParticleTracer(TracerMixin):
                                           f"supported (site '{name}').")
 
         declared = batch.get_shape()
-        family, params = classify(distribution)
+        family, params, extra = _classify(distribution)
         if family == "categorical" and self._validate_parameters and \
                 torch.is_floating_point(data):
             # The kernel reads int64 values and checks only the range; fractional or NaN values
@@ -457,7 +538,8 @@ class ParticleTracer(TracerMixin):
         # parameters as well (MI_FLAG_PARAM), replacing torch's validate_args at construction.
         roles = [self._emit(p) for p in params] + [self._emit(data)]
         record = SiteRecord(name=name, family=family, roles=roles, site_shape=shape, scale=scale,
-                            mask=mask, description=type(distribution).__name__, order=self.order)
+                            mask=mask, description=type(distribution).__name__, order=self.order,
+                            extra=extra)
         if linear is not None:
             record.linear_X = linear.X
             record.linear_theta_index = self._emit(linear.theta)
