@@ -349,6 +349,31 @@ int mi_categorical_forward(const float* logits, int64_t stride_k, int64_t stride
                            uint32_t* flags, void* stream);
 int mi_categorical_workspace_bytes(int64_t K, int64_t N, size_t* bytes);
 
+/* Largest number of categories C = event_shape[0] of a Dirichlet the kernels below take (larger:
+ * MI_EUNSUPPORTED, checked before any device work). */
+#define MI_DIRICHLET_MAX_C 1024
+
+/* Dirichlet site (replaces Dirichlet.log_prob, dirichlet.py:90-97, and its autograd):
+ * concentration[k, i, c] and value[k, i, c] by strides (stride_k = 0 for a particle-constant
+ * tensor), optional mask[i]:
+ *   total[k] = scale * sum_i mask_i * (sum_c xlogy(a_c - 1, x_c) + lgamma(a0) - sum_c lgamma(a_c))
+ * with a0 = sum_c a_c in fp32 (as torch), the lgamma terms and every sum in fp64 in a fixed order
+ * (no atomics). When non-NULL, dconcentration / dvalue (row-major contiguous [K, N, C]) are
+ * written in every entry, zeros on masked rows:
+ *   dconcentration[k, i, c] = g0 * scale * (log x_c + psi(a0) - psi(a_c))     (digamma in fp64)
+ *   dvalue[k, i, c]         = g0 * scale * (a_c - 1) / x_c
+ * following torch's autograd formulas of xlogy at a_c = 1 (no log x_c term where x_c <= 0).
+ * flags[0] (zeroed by this call) = MI_FLAG_PARAM if an observed a_c is not > 0, MI_FLAG_SUPPORT
+ * unless every observed x_c >= 0 and |sum_c x_c - 1| < 1e-6 (torch's simplex, the sum in fp64).
+ * The workspace holds the rows' fp64 log densities. 1 <= C <= MI_DIRICHLET_MAX_C. */
+int mi_dirichlet_forward(const float* concentration, int64_t stride_k, int64_t stride_i,
+                         int64_t stride_c, int64_t K, int64_t N, int64_t C, const float* value,
+                         int64_t value_stride_k, int64_t value_stride_i, int64_t value_stride_c,
+                         const uint8_t* mask, int64_t mask_stride_i, double scale, float g0,
+                         float* dconcentration, float* dvalue, void* workspace,
+                         size_t workspace_bytes, float* total, uint32_t* flags, void* stream);
+int mi_dirichlet_workspace_bytes(int64_t K, int64_t N, int64_t C, size_t* bytes);
+
 /* MultivariateNormal site (replaces MultivariateNormal.log_prob, multivariate_normal.py:255-262,
  * with _batch_mahalanobis at :80-102; sites such as examples/missing-observations.md:42), float64,
  * row-major contiguous value[b, n], loc[b, n] and lower-triangular scale_tril[b, n, n] (the
@@ -508,6 +533,40 @@ int mi_gamma_rsample_backward(const float* dx, int64_t dx_stride_k, int64_t dx_s
                               size_t workspace_bytes, float* dconcentration,
                               int64_t dconcentration_stride, float* drate, int64_t drate_stride,
                               void* stream);
+
+/* Dirichlet(concentration[N, C], row-major contiguous) guide draws (replaces Dirichlet.rsample,
+ * dirichlet.py:85-88 -> torch._sample_dirichlet):
+ *   x[k, n, c] = g[k, n, c] / sum_j g[k, n, j]                     (row-major contiguous [K, N, C])
+ * with g[k, n, c] exactly the standard Gamma variate mi_gamma_rsample draws for (seed, step
+ * (+ *step_device), stream_id, particle_offset + k, element n * C + c) from concentration viewed
+ * as [N * C], or g_in[k, n, c] when g_in != NULL (parity mode). The row sum is taken in fp64 in a
+ * fixed order and each component divided once, then clamped to [FLT_MIN, 1 - 2^-24] as torch does;
+ * a row whose variates all underflow is the (clamped) one-hot of its largest concentration. Row k
+ * of a draw with particle_offset = o is bit-identical to row k + o of the draw with offset 0.
+ * 1 <= C <= MI_DIRICHLET_MAX_C. */
+int mi_dirichlet_rsample(const float* concentration, int64_t K, int64_t N, int64_t C,
+                         uint64_t seed, uint64_t step, const uint64_t* step_device,
+                         uint32_t stream_id, int64_t particle_offset, const float* g_in, float* x,
+                         void* stream);
+/* Backward for upstream dx[k, n, c] (strided) and the saved draws x (dirichlet.py:17-20,
+ * _Dirichlet_backward), fp64, reduced over particles in a fixed order (no atomics; particle slices
+ * are combined through the workspace):
+ *   dconcentration[n, c] = sum_k dgrad(x_kc, a_c, a0) * (dx_kc - sum_j x_kj * dx_kj)
+ * with dgrad torch._dirichlet_grad (ATen/native/Distributions.h dirichlet_grad_one) and a0 the
+ * fp32 row sum of the concentrations. */
+int mi_dirichlet_rsample_backward_workspace_bytes(int64_t K, int64_t N, int64_t C, size_t* bytes);
+int mi_dirichlet_rsample_backward(const float* dx, int64_t dx_stride_k, int64_t dx_stride_i,
+                                  int64_t dx_stride_c, const float* x, const float* concentration,
+                                  int64_t K, int64_t N, int64_t C, void* workspace,
+                                  size_t workspace_bytes, float* dconcentration, void* stream);
+
+/* Dirichlet entropy (dirichlet.py:122-130) of concentration[N, C] (row-major contiguous), summed
+ * over the rows, and its gradient, in one launch, fp64, fixed order:
+ *   entropy[0] = sum_n [sum_c lgamma(a_c) - lgamma(a0) - (C - a0) psi(a0) - sum_c (a_c - 1) psi(a_c)]
+ *   dconcentration[n, c] = (a0 - C) psi'(a0) - (a_c - 1) psi'(a_c)        (when non-NULL)
+ * 1 <= C <= MI_DIRICHLET_MAX_C. */
+int mi_dirichlet_entropy(const float* concentration, int64_t N, int64_t C, float* entropy,
+                         float* dconcentration, void* stream);
 
 /* Constrained parameters of one guide factor in one launch, interleaved [n, m]:
  *   out[i * m + j] = exp(u[j][i * stride[j]])   (transform[j] MI_TRANSFORM_EXP: transform_to(positive),

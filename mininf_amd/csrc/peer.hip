@@ -158,7 +158,8 @@ int mi_peer_allreduce(const mi_peer* peer, const float* in, float* out, int64_t 
 }
 
 int mi_peer_call_count(const mi_peer* peer, uint64_t* count) {
-  if (peer == nullptr || count == nullptr || peer->rank < 0 || peer->rank >= MI_PEER_MAX_RANKS ||
+  if (peer == nullptr || count == nullptr || peer->world < 1 ||
+      peer->world > MI_PEER_MAX_RANKS || peer->rank < 0 || peer->rank >= peer->world ||
       peer->regions[peer->rank] == nullptr || peer->max_floats < 1)
     return MI_EINVAL;
   const uint64_t* counter = reinterpret_cast<const uint64_t*>(

@@ -603,6 +603,69 @@ class _CategoricalFn(torch.autograd.Function):
         return None, None, None, dlogits, None, None
 
 
+def _run_dirichlet(site: SiteRecord, g0: float, conc: torch.Tensor, value: torch.Tensor,
+                   mask: Optional[torch.Tensor], need: Tuple[bool, bool],
+                   flags: Optional[torch.Tensor] = None):
+    """
+    Launch ``mi_dirichlet_forward``: (total [K], speculative dconcentration / dvalue or None,
+    flags [1]). ``need``: which of the two gradients to write.
+    """
+    K, N, C = conc.shape
+    device = conc.device
+    # contiguous [K, N, C], every entry written
+    dconc = torch.empty((K, N, C), dtype=torch.float32, device=device) if need[0] else None
+    dvalue = torch.empty((K, N, C), dtype=torch.float32, device=device) if need[1] else None
+    size = ctypes.c_size_t()
+    lib = nat.lib()
+    nat.check(lib.mi_dirichlet_workspace_bytes(K, N, C, ctypes.byref(size)),
+              "mi_dirichlet_workspace_bytes")
+    workspace = torch.empty(max(1, size.value), dtype=torch.uint8, device=device)
+    total = torch.empty(K, dtype=torch.float32, device=device)
+    if flags is None:
+        flags = torch.empty(1, dtype=torch.int32, device=device)
+    nat.check(lib.mi_dirichlet_forward(
+        conc.data_ptr(), conc.stride(0), conc.stride(1), conc.stride(2), K, N, C,
+        value.data_ptr(), value.stride(0), value.stride(1), value.stride(2),
+        None if mask is None else mask.data_ptr(), 0 if mask is None else mask.stride(1),
+        site.scale, g0, nat.ptr(dconc), nat.ptr(dvalue), workspace.data_ptr(), size.value,
+        total.data_ptr(), flags.data_ptr(), nat.stream_handle(device)), "mi_dirichlet_forward")
+    return total, dconc, dvalue, flags
+
+
+class _DirichletFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, site: SiteRecord, holder: dict, g0: float, conc: torch.Tensor,
+                value: torch.Tensor, mask: Optional[torch.Tensor]):  # type: ignore[override]
+        total, dconc, dvalue, flags = _run_dirichlet(
+            site, g0, conc, value, mask, (conc.requires_grad, value.requires_grad))
+        holder["flags"] = flags
+        ctx.grads = (dconc, dvalue)
+        ctx.g0 = g0
+        return total
+
+    @staticmethod
+    def backward(ctx, g):  # type: ignore[override]
+        g = g.contiguous()
+        for grad in ctx.grads:
+            if grad is not None:
+                K, N, C = grad.shape
+                nat.check(nat.lib().mi_scale_rows(grad.data_ptr(), N * C, 1, K, N * C,
+                                                  g.data_ptr(), ctx.g0,
+                                                  nat.stream_handle(g.device)), "mi_scale_rows")
+        return None, None, None, ctx.grads[0], ctx.grads[1], None
+
+
+def _run_row_site(site: SiteRecord, g0: float, param: torch.Tensor, value: torch.Tensor,
+                  mask: Optional[torch.Tensor], flags: Optional[torch.Tensor] = None):
+    """A categorical or Dirichlet site's launch: (total, dparameter, dvalue, flags)."""
+    if site.family == "dirichlet":
+        return _run_dirichlet(site, g0, param, value, mask,
+                              (param.requires_grad, value.requires_grad), flags)
+    total, dlogits, flags = _run_categorical(site, g0, param, value, mask, param.requires_grad,
+                                             flags)
+    return total, dlogits, None, flags
+
+
 # ------------------------------------------------------------------------------------------------
 # Linear-predictor sites: Normal(X @ theta, sigma) / Bernoulli(logits = X @ theta), fused.
 # ------------------------------------------------------------------------------------------------
@@ -1052,8 +1115,8 @@ class LogJoint:
 
 def plan_groups(trace: ParticleTrace, g0: float, device: torch.device):
     """
-    Prepare every recorded site for launch: categorical sites as (site, logits, value, mask) and
-    the other families packed into site groups sharing their element space and a dense operand.
+    Prepare every recorded site for launch: categorical and Dirichlet sites as (site, logits or
+    concentration, value, mask) and the other families packed into site groups sharing their element space and a dense operand.
     """
     K = trace.K
     groups: List[Tuple[torch.Size, _GroupLauncher]] = []
@@ -1078,6 +1141,22 @@ def plan_groups(trace: ParticleTrace, g0: float, device: torch.device):
             mask = None if site.mask is None else site.mask.to(device).bool().expand(shape) \
                 .reshape(1, N).expand(K, N)
             categorical.append((site, lg, val, mask))
+            continue
+        if site.family == "dirichlet":
+            # planned like a categorical site: (site, concentration, value, mask) as [K, N, C]
+            # views (stride 0 along K for a particle-constant tensor), the mask as [K, N]
+            conc, value = (_to_device(_float(t, site.name), K, device, f"site '{site.name}'",
+                                      False)[0] for t in site.tensors)
+            shape = site.site_shape
+            C = conc.shape[-1]
+            N = int(shape.numel())
+
+            def rows(t: torch.Tensor) -> torch.Tensor:
+                t = t.reshape((K,) + (1,) * (len(shape) + 1 - (t.dim() - 1)) + tuple(t.shape[1:]))
+                return t.expand((K,) + tuple(shape) + (C,)).reshape(K, N, C)
+            mask = None if site.mask is None else site.mask.to(device).bool().expand(shape) \
+                .reshape(1, N).expand(K, N)
+            categorical.append((site, rows(conc), rows(value), mask))
             continue
         shape = site.site_shape
         N = int(shape.numel())
@@ -1223,8 +1302,9 @@ def log_joint(trace: ParticleTrace, g0: float, device: torch.device) -> LogJoint
     pending: List[Tuple[str, dict, List[SiteRecord]]] = []
     for site, lg, val, mask in categorical:
         holder: dict = {}
-        totals.append(_CategoricalFn.apply(site, holder, g0, lg, val, mask))
-        pending.append(("categorical", holder, [site]))
+        fn = _DirichletFn if site.family == "dirichlet" else _CategoricalFn
+        totals.append(fn.apply(site, holder, g0, lg, val, mask))
+        pending.append((site.family, holder, [site]))
     for linear in linears:
         holder = {}
         totals.append(_LinearSiteFn.apply(linear, holder, *linear.inputs()))
@@ -1404,10 +1484,11 @@ def _absorb_factor(factor: EntropyFactor, samples: Dict[str, torch.Tensor], laun
                 uses.append((which, j, -1))
             else:
                 return None
-    for _, logits, _, _ in categorical:
-        if shares(logits):
-            return None
-        others.append(logits)
+    for _, param, value, _ in categorical:   # (logits | concentration, value)
+        for t in (param, value):
+            if shares(t):
+                return None
+            others.append(t)
     others.extend(fallback)
     if len(uses) > nat.MAX_SOURCES or _depends_on(others, z.grad_fn):
         return None
@@ -1459,7 +1540,8 @@ def _elbo_workspace(device: torch.device, nbytes: int) -> torch.Tensor:
 class _ElboPlan:
     """
     Everything one ELBO evaluation launches, in the order of the autograd inputs:
-    site groups (their operand tensors), categorical sites (logits, value, mask), linear sites
+    site groups (their operand tensors), categorical / Dirichlet sites (logits | concentration,
+    value, mask), linear sites
     (theta, sigma), torch-evaluated sites (their [K] log densities) and the entropy factors (their
     parameter tensor, or -- absorbed -- the unconstrained parameters of both parameters).
     """
@@ -1684,13 +1766,12 @@ class _ElboPlan:
         cat_results = []
         for j, ((site, lg, val, mask), holder) in enumerate(zip(self.categorical,
                                                                  self.cat_holders)):
-            total, dlogits, flags = _run_categorical(site, self.g0, lg, val, mask,
-                                                     lg.requires_grad, self.flags[j:j + 1])
+            total, dparam, dvalue, flags = _run_row_site(site, self.g0, lg, val, mask,
+                                                         self.flags[j:j + 1])
             holder["flags"] = flags
             terms.append(total)
-            if dlogits is not None:
-                buffers.append(dlogits)
-            cat_results.append(dlogits)
+            buffers.extend(g for g in (dparam, dvalue) if g is not None)
+            cat_results.append((dparam, dvalue))
         lin_results = []
         base = len(self.categorical)
         for j, (linear, holder) in enumerate(zip(self.linears, self.lin_holders)):
@@ -1837,7 +1918,8 @@ class _ElboPlan:
         no draw launch); deferred_reductions: site
         reductions finished by the ELBO forward; final_grads: the forward wrote the guide
         gradients (no backward launch for loss.backward()); optimizer_step: the Adam step ran in the held launch's last block (no launch of its own);
-        mvn_draws: MultivariateNormal guide factors drawn by the native sampler (mi_mvn_rsample).
+        mvn_draws: MultivariateNormal guide factors drawn by the native sampler (mi_mvn_rsample);
+        dirichlet_draws: Dirichlet guide factors drawn by the native sampler (mi_dirichlet_rsample).
         """
         return {
             "folded_priors": sum(l.prior is not None for l in self.launchers) +
@@ -1851,6 +1933,7 @@ class _ElboPlan:
             "final_grads": int(getattr(self, "final", None) is not None),
             "optimizer_step": 0,   # set when the optimizer step joins the held launch
             "mvn_draws": guide.mvn_draws(),
+            "dirichlet_draws": guide.dirichlet_draws(),
         }
 
     def _reduce_ok(self, assume=None) -> bool:
@@ -1950,8 +2033,8 @@ class _ElboPlan:
                     out.append(slot_grad[op.slot].reshape(launcher.K, 1))
                 else:
                     out.append(None)
-        for dlogits in cat_results:
-            out.extend([dlogits, None, None])
+        for dparam, dvalue in cat_results:
+            out.extend([dparam, dvalue, None])
         for j, (linear, dslots) in enumerate(zip(self.linears, lin_results)):
             dtheta, dsigma = linear.grads(dslots)
             out.append(None if ("lin_theta", j) in self.skip_lin else dtheta)
@@ -2214,7 +2297,7 @@ def _materialize_draws(trace: ParticleTrace, draws) -> None:
 def _lazy_uses(trace: ParticleTrace) -> Tuple[set, set]:
     """
     (all lazy draws in the trace's site tensors, those used where the kernels cannot compute
-    them: linear / categorical sites, or broadcast beyond the draw's own shape).
+    them: linear / categorical / Dirichlet sites, or broadcast beyond the draw's own shape).
     """
     seen, bad = set(), set()
     for site in trace.sites:
@@ -2223,7 +2306,7 @@ def _lazy_uses(trace: ParticleTrace) -> Tuple[set, set]:
             if lazy is None:
                 continue
             seen.add(lazy)
-            if site.linear_X is not None or site.family == "categorical" or \
+            if site.linear_X is not None or site.family in ("categorical", "dirichlet") or \
                     tuple(t.shape[1:]) != tuple(site.site_shape) or \
                     int(site.site_shape.numel()) != lazy.N:
                 bad.add(lazy)
@@ -2233,7 +2316,8 @@ def _lazy_uses(trace: ParticleTrace) -> Tuple[set, set]:
 def entropy_factors(approximation) -> Tuple[List[EntropyFactor], list]:
     """
     Split a factorised guide into factors whose entropy the ELBO kernels evaluate (Normal, Beta,
-    Gamma) and the rest (whose entropy torch.distributions evaluates).
+    Gamma) and the rest (whose entropy torch.distributions evaluates, or -- a native Dirichlet
+    factor, guide.native_dirichlet -- mi_dirichlet_entropy, called by the loss).
     """
     from torch.distributions import Beta, Gamma, Normal
 
@@ -2319,7 +2403,7 @@ def elbo(trace: ParticleTrace, g0: float, device: torch.device, factors: List[En
     LAST_FUSIONS = plan.fusions()
     pending: List[Tuple[str, dict, List[SiteRecord]]] = []
     for (site, _, _, _), holder in zip(categorical, plan.cat_holders):
-        pending.append(("categorical", holder, [site]))
+        pending.append((site.family, holder, [site]))
     for linear, holder in zip(linears, plan.lin_holders):
         pending.append(("linear", holder, linear.flag_sites))
     for launcher, holder in zip(launchers, plan.holders):

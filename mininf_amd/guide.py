@@ -2,16 +2,17 @@
 Reparameterised guide sampling over K particles (replaces ``FactorizedDistribution.rsample``,
 reference ``mininf/nn.py:133-145``, with ONE draw per call at ``nn.py:217``).
 
-Normal, Beta, Gamma and full-covariance MultivariateNormal factors are drawn by HIP kernels from a
-counter-based Philox generator keyed by (seed, step, factor index, global particle index, element),
-so that K particles split over W GPUs draw exactly the union of what one GPU would draw. Other
-families (and a batched, float64, host-resident or D > MI_MVN_MAX_N MultivariateNormal) use their
-own ``torch.distributions`` ``rsample`` on the device.
+Normal, Beta, Gamma, Dirichlet and full-covariance MultivariateNormal factors are drawn by HIP
+kernels from a counter-based Philox generator keyed by (seed, step, factor index, global particle
+index, element), so that K particles split over W GPUs draw exactly the union of what one GPU would
+draw. Other families (and a batched, float64, host-resident or D > MI_MVN_MAX_N
+MultivariateNormal; a subclassed, float64, host-resident or C > MI_DIRICHLET_MAX_C Dirichlet) use
+their own ``torch.distributions`` ``rsample`` on the device.
 
 Parity mode: ``noise[name]`` injects host-drawn standard normals (Normal factors, [K, *shape];
 MultivariateNormal factors, [K, D]), the draws themselves (Beta factors) or the standard Gamma
-draws g with x = g / rate (Gamma factors), exactly as the oracle's sample-injection protocol does
-(SURVEY.md 8(c)).
+draws g with x = g / rate (Gamma factors) or x = g / sum(g) (Dirichlet factors, [K, *batch, C]),
+exactly as the oracle's sample-injection protocol does.
 """
 from __future__ import annotations
 
@@ -21,7 +22,7 @@ import os
 from typing import Dict, Optional, Tuple
 
 import torch
-from torch.distributions import Beta, Distribution, Gamma, MultivariateNormal, Normal
+from torch.distributions import Beta, Dirichlet, Distribution, Gamma, MultivariateNormal, Normal
 
 from . import _native as nat
 
@@ -449,6 +450,99 @@ def mvn_draws() -> int:
     return _MVN_DRAWS
 
 
+def native_dirichlet(distribution) -> bool:
+    """
+    Whether a Dirichlet guide factor is drawn by mi_dirichlet_rsample (and its entropy evaluated by
+    mi_dirichlet_entropy): exactly a Dirichlet (a subclass may override rsample), float32, on the
+    device, C <= MI_DIRICHLET_MAX_C. Any other Dirichlet keeps torch's own rsample and entropy.
+    """
+    if type(distribution) is not Dirichlet:
+        return False
+    conc = distribution.concentration
+    return isinstance(conc, torch.Tensor) and conc.is_cuda and conc.dtype == torch.float32 and \
+        1 <= int(conc.shape[-1]) <= nat.DIRICHLET_MAX_C
+
+
+def _dirichlet_rows(distribution: Dirichlet) -> torch.Tensor:
+    """The concentration as a contiguous [N, C] array (N = numel(batch_shape))."""
+    conc = distribution.concentration
+    fill_exp(conc)
+    C = int(conc.shape[-1])
+    return conc.reshape(max(1, int(distribution.batch_shape.numel())), C).contiguous()
+
+
+class _DirichletRsampleFn(torch.autograd.Function):
+    """
+    Dirichlet.rsample (dirichlet.py:85-88) over K particles: normalised standard Gamma draws by
+    mi_dirichlet_rsample, and _Dirichlet_backward (dirichlet.py:17-20) in fp64 from the saved
+    draws (mi_dirichlet_rsample_backward). ``cfg.noise`` injects the standard Gamma draws g
+    [K, N, C], as for a Gamma factor.
+    """
+    @staticmethod
+    def forward(ctx, cfg: DrawConfig, conc: torch.Tensor):  # type: ignore[override]
+        (N, C), K = conc.shape, cfg.K
+        x = torch.empty((K, N, C), dtype=torch.float32, device=conc.device)
+        seed, step = _philox_key(cfg)
+        nat.check(nat.lib().mi_dirichlet_rsample(
+            conc.data_ptr(), K, N, C, seed, step, nat.ptr(cfg.step_device), cfg.stream_id,
+            cfg.particle_offset, nat.ptr(cfg.noise), x.data_ptr(),
+            nat.stream_handle(conc.device)), "mi_dirichlet_rsample")
+        ctx.save_for_backward(x, conc)
+        return x
+
+    @staticmethod
+    def backward(ctx, dx: torch.Tensor):  # type: ignore[override]
+        x, conc = ctx.saved_tensors
+        K, N, C = x.shape
+        device = x.device
+        if dx.dtype != torch.float32:
+            dx = dx.to(torch.float32)
+        size = ctypes.c_size_t()
+        lib = nat.lib()
+        nat.check(lib.mi_dirichlet_rsample_backward_workspace_bytes(K, N, C, ctypes.byref(size)),
+                  "mi_dirichlet_rsample_backward_workspace_bytes")
+        workspace = torch.empty(max(1, size.value), dtype=torch.uint8, device=device)
+        dconc = torch.empty((N, C), dtype=torch.float32, device=device)
+        nat.check(lib.mi_dirichlet_rsample_backward(
+            dx.data_ptr(), dx.stride(0), dx.stride(1), dx.stride(2), x.data_ptr(), conc.data_ptr(),
+            K, N, C, workspace.data_ptr(), size.value, dconc.data_ptr(),
+            nat.stream_handle(device)), "mi_dirichlet_rsample_backward")
+        return None, dconc
+
+
+class _DirichletEntropyFn(torch.autograd.Function):
+    """Dirichlet.entropy().sum() (dirichlet.py:122-130) and its gradient in one launch
+    (mi_dirichlet_entropy); the backward scales the stored gradient."""
+    @staticmethod
+    def forward(ctx, conc: torch.Tensor):  # type: ignore[override]
+        N, C = conc.shape
+        out = torch.empty((), dtype=torch.float32, device=conc.device)
+        grad = torch.empty_like(conc) if conc.requires_grad else None
+        nat.check(nat.lib().mi_dirichlet_entropy(
+            conc.data_ptr(), N, C, out.data_ptr(), nat.ptr(grad),
+            nat.stream_handle(conc.device)), "mi_dirichlet_entropy")
+        ctx.grad = grad
+        return out
+
+    @staticmethod
+    def backward(ctx, g: torch.Tensor):  # type: ignore[override]
+        return None if ctx.grad is None else ctx.grad * g
+
+
+def dirichlet_entropy(distribution: Dirichlet) -> torch.Tensor:
+    """The summed entropy of a :func:`native_dirichlet` guide factor (0-d, differentiable)."""
+    return _DirichletEntropyFn.apply(_dirichlet_rows(distribution))
+
+
+# factors the native Dirichlet sampler drew in the last draw_all
+# (EvidenceLowerBoundLoss.last_fusions["dirichlet_draws"])
+_DIRICHLET_DRAWS = 0
+
+
+def dirichlet_draws() -> int:
+    return _DIRICHLET_DRAWS
+
+
 # ---- deferred small Normal draws ---------------------------------------------------------------
 # A small Normal factor's [K, N] draw (the regression's theta, N = P features) is made by the loss's
 # planning instead of when the guide is drawn: when the only kernel that reads it is one linear
@@ -756,6 +850,16 @@ def draw(distribution: Distribution, cfg: DrawConfig, lazy: bool = False) -> tor
                 .contiguous()
         _MVN_DRAWS += 1
         return _MvnRsampleFn.apply(cfg, loc, scale_tril)
+    if native_dirichlet(distribution):
+        global _DIRICHLET_DRAWS
+        conc = _dirichlet_rows(distribution)
+        N, C = conc.shape
+        if cfg.noise is not None:   # injected standard draws g, [K, *batch, C]
+            cfg.noise = cfg.noise.to(device=conc.device, dtype=torch.float32) \
+                .reshape(cfg.K, N, C).contiguous()
+        _DIRICHLET_DRAWS += 1
+        x = _DirichletRsampleFn.apply(cfg, conc)
+        return x.reshape((cfg.K,) + tuple(distribution.batch_shape) + (C,))
     if cfg.noise is not None:
         return cfg.noise
     return distribution.rsample(torch.Size([cfg.K]))
@@ -772,10 +876,10 @@ def draw_all(approximation: Dict[str, Distribution], K: int, seed: int, step: in
     Normal factors become :class:`LazyDraw` placeholders evaluated inside the site kernels.
     ``element_offsets``: global index of element 0 of data-sharded factors (multiples of 4).
     """
-    global _MVN_DRAWS
+    global _MVN_DRAWS, _DIRICHLET_DRAWS
     _LAZY.clear()
     _DRAWN.clear()
-    _MVN_DRAWS = 0
+    _MVN_DRAWS = _DIRICHLET_DRAWS = 0
     flush_draws(claimed=True)
     samples = {}
     for stream_id, (name, factor) in enumerate(approximation.items()):

@@ -429,13 +429,15 @@ class EvidenceLowerBoundLoss(nn.Module):
             called with are the rank's slice. Shared factors and sites count 1/W per rank, the
             sharded factors draw their slice of the global draw.
 
-    Guide factors of type Normal, Beta, Gamma and MultivariateNormal (unbatched, float32, on the
-    device, at most 1024 dimensions; any of its three parameterisations) are drawn by the native
-    samplers: ``seed`` governs their draws, particle shards draw the union of what one device
-    would draw, and a captured step draws anew on every replay. Their entropy is evaluated inside
-    the ELBO kernels. Every other factor uses its own ``rsample`` (torch's generator) and
-    ``entropy``. ``last_fusions`` reports the fast paths the last evaluation took, among them
-    ``mvn_draws``, the number of factors the native MultivariateNormal sampler drew.
+    Guide factors of type Normal, Beta, Gamma, MultivariateNormal (unbatched, float32, on the
+    device, at most 1024 dimensions; any of its three parameterisations) and Dirichlet (float32, on
+    the device, at most 1024 categories) are drawn by the native samplers: ``seed`` governs their
+    draws, particle shards draw the union of what one device would draw, and a captured step draws
+    anew on every replay. Their entropy is evaluated inside the ELBO kernels (Dirichlet: by its own
+    kernel, ``mi_dirichlet_entropy``). Every other factor uses its own ``rsample`` (torch's
+    generator) and ``entropy``. ``last_fusions`` reports the fast paths the last evaluation took,
+    among them ``mvn_draws`` and ``dirichlet_draws``, the numbers of factors the native
+    MultivariateNormal and Dirichlet samplers drew.
 
     Example:
 
@@ -616,8 +618,11 @@ class EvidenceLowerBoundLoss(nn.Module):
                 guide.release_lazy()
             if rest:
                 names = {id(f): name for name, f in approximation.items()}
+                # (a native Dirichlet factor: value and gradient by mi_dirichlet_entropy)
                 extra = cast(torch.Tensor, sum(
-                    f.entropy().sum() / (world if shared is None or names[id(f)] in shared else 1)
+                    (guide.dirichlet_entropy(f) if guide.native_dirichlet(f)
+                     else f.entropy().sum()) /
+                    (world if shared is None or names[id(f)] in shared else 1)
                     for f in rest))
                 engine.flush_pending_step()
                 loss = loss - extra

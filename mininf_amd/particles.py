@@ -28,7 +28,8 @@ import weakref
 from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, cast
 
 import torch
-from torch.distributions import Bernoulli, Beta, Binomial, Categorical, Cauchy, Distribution, \
+from torch.distributions import Bernoulli, Beta, Binomial, Categorical, Cauchy, Dirichlet, \
+    Distribution, \
     Exponential, ExpTransform, Gamma, HalfCauchy, HalfNormal, Laplace, LogNormal, \
     MultivariateNormal, NegativeBinomial, Normal, Poisson, PowerTransform, StudentT, \
     TransformedDistribution
@@ -37,7 +38,7 @@ from torch.distributions.utils import lazy_property
 from torch.overrides import TorchFunctionMode
 from torch.utils._pytree import tree_flatten, tree_map
 
-from . import core, data, graph, mvn, predictive
+from . import _native, core, data, graph, mvn, predictive
 from .distributions import InverseGamma
 from .core import batch, no_log_prob, State, TracerMixin, Value, validate_shape
 from .util import _normalize_shape, check_constraint, OptionalSize
@@ -96,7 +97,7 @@ class SiteRecord:
 
     ``roles`` holds output indices into the vmapped function's outputs for the family's roles
     (Normal: loc, scale, value; Bernoulli: logits|probs, value; Beta: concentration1,
-    concentration0, value; Categorical: logits, value). After :func:`trace_particles` returns,
+    concentration0, value; Categorical: logits, value; Dirichlet: concentration, value). After :func:`trace_particles` returns,
     ``tensors`` holds the corresponding [K, ...] tensors.
     """
     name: str
@@ -314,6 +315,8 @@ def _classify(distribution: Distribution) -> Tuple[str, List[Any], float]:
         return "beta", [distribution.concentration1, distribution.concentration0], 0.0
     if cls is Categorical:
         return "categorical", [distribution.logits], 0.0
+    if cls is Dirichlet and _kernel_dirichlet(distribution):
+        return "dirichlet", [distribution.concentration], 0.0
     if cls is Gamma:
         return "gamma", [distribution.concentration, distribution.rate], 0.0
     if cls is Poisson:
@@ -351,6 +354,14 @@ def _classify(distribution: Distribution) -> Tuple[str, List[Any], float]:
     if cls is NegativeBinomial:
         return "negative_binomial", [distribution.total_count, distribution.logits], 0.0
     return "torch", [], 0.0
+
+
+def _kernel_dirichlet(distribution: Dirichlet) -> bool:
+    """A Dirichlet the site kernel takes (mi_dirichlet_forward): a float32 concentration of at
+    most MI_DIRICHLET_MAX_C categories. Any other keeps the torch path."""
+    concentration = distribution.concentration
+    return isinstance(concentration, torch.Tensor) and concentration.dtype == torch.float32 and \
+        1 <= int(concentration.shape[-1]) <= _native.DIRICHLET_MAX_C
 
 
 def _is_log_normal(distribution: Distribution) -> bool:
@@ -501,8 +512,15 @@ class ParticleTracer(TracerMixin):
             # The kernel reads int64 values and checks only the range; fractional or NaN values
             # (integer_interval's `value % 1 == 0`, constraints.py) are checked here (memoised).
             self._check_support(name, value, distribution, cast(Constraint, distribution.support))
+        if family == "dirichlet" and (data.dtype != torch.float32 or data.dim() < 1 or
+                                      data.shape[-1] != distribution.event_shape[0]):
+            family, params = "torch", []   # the kernel reads float32 rows of C categories
         if family == "categorical":
             shape = broadcast_shapes(tuple(data.shape), tuple(distribution.batch_shape))
+        elif family == "dirichlet":
+            shape = broadcast_shapes(tuple(data.shape[:-1]), tuple(distribution.batch_shape))
+            if mask is not None:
+                mask = mask.all(-1)   # a row is observed when all its categories are
         elif family != "torch":
             shape = broadcast_shapes(tuple(data.shape), *[tuple(p.shape) for p in params])
         else:
@@ -533,6 +551,8 @@ class ParticleTracer(TracerMixin):
                 linear = info.root or info
             params = [p if (linear is not None and j == 0) else mode.materialize(p)
                       for j, p in enumerate(params)]
+            if family == "dirichlet":
+                data = mode.materialize(data)
 
         # Value support is checked by the site kernels (fused flag); constraint checks on the
         # parameters as well (MI_FLAG_PARAM), replacing torch's validate_args at construction.
