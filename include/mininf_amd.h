@@ -458,6 +458,42 @@ int mi_mvn_rsample_backward(const float* dz, int64_t dz_stride_k, int64_t dz_str
                             void* workspace, size_t workspace_bytes,
                             float* dloc, float* dscale_tril, void* stream);
 
+/* LowRankMultivariateNormal guide factor (replaces LowRankMultivariateNormal.rsample, torch 2.10
+ * lowrank_multivariate_normal.py:214-223, over K particles): loc[D], row-major contiguous
+ * cov_factor[D, R], cov_diag[D] > 0, covariance cov_factor cov_factor^T + diag(cov_diag), and
+ *   z[k, i] = loc[i] + sum_r cov_factor[i, r] * eps_W[k, r] + sqrt(cov_diag[i]) * eps_D[k, i]
+ * (row-major [K, D]). Both sets of normals come from the factor's one Normal stream (seed,
+ * step (+ *step_device), stream_id, particle_offset + k): eps_D[k, i] is element i, exactly what
+ * mi_normal_rsample / mi_philox_normal produce for it, and eps_W[k, r] is element Dpad + r with
+ * Dpad = 4 * ceil(D / 4) (both parts start on a Philox quad). A non-NULL `eps` is read instead
+ * (parity mode): row-major [K, D + R], the D columns of eps_D first, then the R of eps_W.
+ * Each z[k, i] is one fp32 chain: acc = loc[i]; acc = fma(eps_W[k, r], cov_factor[i, r], acc) for
+ * r ascending (on v_mfma_f32_32x32x2_f32 for R >= 32, zero-padded to whole tiles of r);
+ * acc = fma(sqrtf(cov_diag[i]), eps_D[k, i], acc) with a correctly rounded square root. Row k of a
+ * draw with particle_offset = o is bit-identical to row k + o of the draw with particle_offset = 0,
+ * for any K. 1 <= R <= MI_LOWRANK_MAX_R, 1 <= D <= MI_LOWRANK_MAX_D (larger: MI_EUNSUPPORTED),
+ * K >= 1; checked before any device work. */
+#define MI_LOWRANK_MAX_R 128
+#define MI_LOWRANK_MAX_D (1 << 24)
+int mi_lowrank_rsample(const float* loc, const float* cov_factor, const float* cov_diag,
+                       int64_t K, int64_t D, int64_t R, uint64_t seed, uint64_t step,
+                       const uint64_t* step_device, uint32_t stream_id, int64_t particle_offset,
+                       const float* eps, float* z, void* stream);
+
+/* Backward of mi_lowrank_rsample for upstream dz[k, i] (strided), reduced over particles in a
+ * fixed order (no atomics; particle slices are combined in fp64 through the workspace):
+ *   dloc[i]           = sum_k dz[k, i]
+ *   dcov_factor[i, r] = sum_k dz[k, i] * eps_W[k, r]
+ *   dcov_diag[i]      = (sum_k dz[k, i] * eps_D[k, i]) * 0.5 / sqrt(cov_diag[i])
+ * with the normals regenerated from the counter (or read from `eps`); the forward stores none. */
+int mi_lowrank_rsample_backward_workspace_bytes(int64_t K, int64_t D, int64_t R, size_t* bytes);
+int mi_lowrank_rsample_backward(const float* dz, int64_t dz_stride_k, int64_t dz_stride_i,
+                                const float* cov_diag, int64_t K, int64_t D, int64_t R,
+                                uint64_t seed, uint64_t step, const uint64_t* step_device,
+                                uint32_t stream_id, int64_t particle_offset, const float* eps,
+                                void* workspace, size_t workspace_bytes, float* dloc,
+                                float* dcov_factor, float* dcov_diag, void* stream);
+
 /* Beta(concentration1, concentration0) draws x[k, i] = G1 / (G1 + G0) with Marsaglia-Tsang gamma
  * variates from the same counter-based generator (beta.py:85-86, dirichlet.py:23-36, 85-88). With
  * `x_in` non-NULL the draws are copied from it instead (parity mode). */

@@ -30,6 +30,8 @@ LINEAR_MAX_P = 64
 LINEAR_VALU = 2
 MVN_MAX_N = 1024   # MI_MVN_MAX_N
 DIRICHLET_MAX_C = 1024   # MI_DIRICHLET_MAX_C
+LOWRANK_MAX_R = 128   # MI_LOWRANK_MAX_R
+LOWRANK_MAX_D = 1 << 24   # MI_LOWRANK_MAX_D
 
 NORMAL, BERNOULLI_LOGITS, BERNOULLI_PROBS, BETA, GAMMA, POISSON, INVERSE_GAMMA = 0, 1, 2, 3, 4, 5, 6
 EXPONENTIAL, LAPLACE, CAUCHY, HALF_NORMAL, HALF_CAUCHY, LOG_NORMAL = 7, 8, 9, 10, 11, 12
@@ -280,6 +282,15 @@ _SIGNATURES = {
     "mi_mvn_rsample_backward": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, ctypes.c_uint64,
                                                ctypes.c_uint64, c_vp, ctypes.c_uint32, c_i64,
                                                c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp, c_vp]),
+    "mi_lowrank_rsample": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, ctypes.c_uint64,
+                                          ctypes.c_uint64, c_vp, ctypes.c_uint32, c_i64, c_vp,
+                                          c_vp, c_vp]),
+    "mi_lowrank_rsample_backward_workspace_bytes": (ctypes.c_int, [
+        c_i64, c_i64, c_i64, ctypes.POINTER(ctypes.c_size_t)]),
+    "mi_lowrank_rsample_backward": (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64,
+                                                   ctypes.c_uint64, ctypes.c_uint64, c_vp,
+                                                   ctypes.c_uint32, c_i64, c_vp, c_vp,
+                                                   ctypes.c_size_t, c_vp, c_vp, c_vp, c_vp]),
     "mi_beta_rsample": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, ctypes.c_uint64,
                                        ctypes.c_uint64, c_vp, ctypes.c_uint32, c_i64, c_vp, c_vp,
                                        c_vp]),

@@ -1,7 +1,7 @@
 """
 In-tree build of ``libmininf_amd.so`` (gfx950). Used by ``__graft_entry__.build()`` and the tests.
 
-The library holds the precompiled kernels (sites.hip, guide.hip, mvn_guide.hip, dirichlet.hip, elbo.hip, linear.hip) and the host-side site-program
+The library holds the precompiled kernels (sites.hip, guide.hip, mvn_guide.hip, lowrank_guide.hip, dirichlet.hip, elbo.hip, linear.hip) and the host-side site-program
 specialiser (jit.cpp), which embeds ``include/mininf_amd.h`` and ``csrc/device_math.hpp`` verbatim
 so that kernels compiled at trace time by hiprtc share the exact device math of the precompiled
 ones.
@@ -18,7 +18,8 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(ROOT, "include")
 SOURCES = [os.path.join(CSRC, name)
            for name in ("sites.hip", "guide.hip", "elbo.hip", "linear.hip", "minibatch.hip",
-                        "adam.hip", "mvn.hip", "mvn_guide.hip", "dirichlet.hip", "peer.hip", "jit.cpp")]
+                        "adam.hip", "mvn.hip", "mvn_guide.hip", "lowrank_guide.hip", "dirichlet.hip",
+                        "peer.hip", "jit.cpp")]
 HEADERS = [os.path.join(CSRC, name) for name in ("common.hpp", "device_math.hpp", "beta_grad.hpp",
                                                  "gamma_sample.hpp", "jit.hpp",
                                                  "internal.hpp", "entropy.hpp", "adam_math.hpp")] + \

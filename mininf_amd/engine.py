@@ -1919,7 +1919,9 @@ class _ElboPlan:
         reductions finished by the ELBO forward; final_grads: the forward wrote the guide
         gradients (no backward launch for loss.backward()); optimizer_step: the Adam step ran in the held launch's last block (no launch of its own);
         mvn_draws: MultivariateNormal guide factors drawn by the native sampler (mi_mvn_rsample);
-        dirichlet_draws: Dirichlet guide factors drawn by the native sampler (mi_dirichlet_rsample).
+        dirichlet_draws: Dirichlet guide factors drawn by the native sampler (mi_dirichlet_rsample);
+        lowrank_draws: LowRankMultivariateNormal guide factors drawn by the native sampler
+        (mi_lowrank_rsample).
         """
         return {
             "folded_priors": sum(l.prior is not None for l in self.launchers) +
@@ -1934,6 +1936,7 @@ class _ElboPlan:
             "optimizer_step": 0,   # set when the optimizer step joins the held launch
             "mvn_draws": guide.mvn_draws(),
             "dirichlet_draws": guide.dirichlet_draws(),
+            "lowrank_draws": guide.lowrank_draws(),
         }
 
     def _reduce_ok(self, assume=None) -> bool:
@@ -2317,7 +2320,10 @@ def entropy_factors(approximation) -> Tuple[List[EntropyFactor], list]:
     """
     Split a factorised guide into factors whose entropy the ELBO kernels evaluate (Normal, Beta,
     Gamma) and the rest (whose entropy torch.distributions evaluates, or -- a native Dirichlet
-    factor, guide.native_dirichlet -- mi_dirichlet_entropy, called by the loss).
+    factor, guide.native_dirichlet -- mi_dirichlet_entropy, called by the loss). A
+    LowRankMultivariateNormal factor stays in the rest also when its draws are native
+    (guide.native_lowrank): its entropy is torch's, and with it the loss is no longer the fused
+    node alone, so its gradients take autograd, never the direct-to-leaf paths.
     """
     from torch.distributions import Beta, Gamma, Normal
 

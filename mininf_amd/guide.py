@@ -2,15 +2,17 @@
 Reparameterised guide sampling over K particles (replaces ``FactorizedDistribution.rsample``,
 reference ``mininf/nn.py:133-145``, with ONE draw per call at ``nn.py:217``).
 
-Normal, Beta, Gamma, Dirichlet and full-covariance MultivariateNormal factors are drawn by HIP
-kernels from a counter-based Philox generator keyed by (seed, step, factor index, global particle
+Normal, Beta, Gamma, Dirichlet, full-covariance MultivariateNormal and LowRankMultivariateNormal
+factors are drawn by HIP kernels from a counter-based Philox generator keyed by (seed, step, factor index, global particle
 index, element), so that K particles split over W GPUs draw exactly the union of what one GPU would
 draw. Other families (and a batched, float64, host-resident or D > MI_MVN_MAX_N
-MultivariateNormal; a subclassed, float64, host-resident or C > MI_DIRICHLET_MAX_C Dirichlet) use
+MultivariateNormal; a subclassed, float64, host-resident or C > MI_DIRICHLET_MAX_C Dirichlet; a
+batched, subclassed, float64, host-resident or R > MI_LOWRANK_MAX_R LowRankMultivariateNormal) use
 their own ``torch.distributions`` ``rsample`` on the device.
 
 Parity mode: ``noise[name]`` injects host-drawn standard normals (Normal factors, [K, *shape];
-MultivariateNormal factors, [K, D]), the draws themselves (Beta factors) or the standard Gamma
+MultivariateNormal factors, [K, D]; LowRankMultivariateNormal factors, [K, D + R]: eps_D, then
+eps_W), the draws themselves (Beta factors) or the standard Gamma
 draws g with x = g / rate (Gamma factors) or x = g / sum(g) (Dirichlet factors, [K, *batch, C]),
 exactly as the oracle's sample-injection protocol does.
 """
@@ -22,7 +24,8 @@ import os
 from typing import Dict, Optional, Tuple
 
 import torch
-from torch.distributions import Beta, Dirichlet, Distribution, Gamma, MultivariateNormal, Normal
+from torch.distributions import Beta, Dirichlet, Distribution, Gamma, LowRankMultivariateNormal, \
+    MultivariateNormal, Normal
 
 from . import _native as nat
 
@@ -450,6 +453,81 @@ def mvn_draws() -> int:
     return _MVN_DRAWS
 
 
+def native_lowrank(distribution) -> bool:
+    """
+    Whether a LowRankMultivariateNormal guide factor is drawn by mi_lowrank_rsample: exactly that
+    class (a subclass may override rsample), unbatched, float32, on the device,
+    R <= MI_LOWRANK_MAX_R and D <= MI_LOWRANK_MAX_D. Any other keeps torch's own rsample. The
+    entropy is torch's in either case.
+    """
+    if type(distribution) is not LowRankMultivariateNormal or \
+            tuple(distribution.batch_shape) != ():
+        return False
+    loc = distribution.loc
+    W, diag = distribution._unbroadcasted_cov_factor, distribution._unbroadcasted_cov_diag
+    return loc.is_cuda and all(t.dtype == torch.float32 for t in (loc, W, diag)) and \
+        W.dim() == 2 and diag.dim() == 1 and \
+        1 <= int(W.shape[-1]) <= nat.LOWRANK_MAX_R and \
+        1 <= int(distribution.event_shape[0]) <= nat.LOWRANK_MAX_D
+
+
+class _LowRankRsampleFn(torch.autograd.Function):
+    """
+    LowRankMultivariateNormal.rsample (lowrank_multivariate_normal.py:214-223) over K particles:
+    z = loc + eps_W @ cov_factor^T + sqrt(cov_diag) * eps_D by mi_lowrank_rsample, both sets of
+    normals from the factor's one Normal stream (eps_D: elements [0, D); eps_W: elements
+    [Dpad, Dpad + R)); the backward regenerates them (mi_lowrank_rsample_backward).
+    ``cfg.noise`` injects [K, D + R]: eps_D, then eps_W.
+    """
+    @staticmethod
+    def forward(ctx, cfg: DrawConfig, loc: torch.Tensor, cov_factor: torch.Tensor,
+                cov_diag: torch.Tensor):  # type: ignore[override]
+        (D, R), K = cov_factor.shape, cfg.K
+        z = torch.empty((K, D), dtype=torch.float32, device=loc.device)
+        seed, step = _philox_key(cfg)
+        nat.check(nat.lib().mi_lowrank_rsample(
+            loc.data_ptr(), cov_factor.data_ptr(), cov_diag.data_ptr(), K, D, R, seed, step,
+            nat.ptr(cfg.step_device), cfg.stream_id, cfg.particle_offset, nat.ptr(cfg.noise),
+            z.data_ptr(), nat.stream_handle(loc.device)), "mi_lowrank_rsample")
+        ctx.cfg = cfg
+        ctx.save_for_backward(cov_diag)
+        ctx.shape = (D, R)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz: torch.Tensor):  # type: ignore[override]
+        cfg: DrawConfig = ctx.cfg
+        (cov_diag,) = ctx.saved_tensors
+        (D, R), K = ctx.shape, cfg.K
+        device = dz.device
+        if dz.dtype != torch.float32:
+            dz = dz.to(torch.float32)
+        size = ctypes.c_size_t()
+        lib = nat.lib()
+        nat.check(lib.mi_lowrank_rsample_backward_workspace_bytes(K, D, R, ctypes.byref(size)),
+                  "mi_lowrank_rsample_backward_workspace_bytes")
+        workspace = torch.empty(max(1, size.value), dtype=torch.uint8, device=device)
+        dloc = torch.empty(D, dtype=torch.float32, device=device)
+        dfactor = torch.empty((D, R), dtype=torch.float32, device=device)
+        ddiag = torch.empty(D, dtype=torch.float32, device=device)
+        seed, step = _philox_key(cfg)
+        nat.check(lib.mi_lowrank_rsample_backward(
+            dz.data_ptr(), dz.stride(0), dz.stride(1), cov_diag.data_ptr(), K, D, R, seed, step,
+            nat.ptr(backward_step(cfg)), cfg.stream_id, cfg.particle_offset, nat.ptr(cfg.noise),
+            workspace.data_ptr(), size.value, dloc.data_ptr(), dfactor.data_ptr(),
+            ddiag.data_ptr(), nat.stream_handle(device)), "mi_lowrank_rsample_backward")
+        return None, dloc, dfactor, ddiag
+
+
+# factors the native LowRankMultivariateNormal sampler drew in the last draw_all
+# (EvidenceLowerBoundLoss.last_fusions["lowrank_draws"])
+_LOWRANK_DRAWS = 0
+
+
+def lowrank_draws() -> int:
+    return _LOWRANK_DRAWS
+
+
 def native_dirichlet(distribution) -> bool:
     """
     Whether a Dirichlet guide factor is drawn by mi_dirichlet_rsample (and its entropy evaluated by
@@ -860,6 +938,20 @@ def draw(distribution: Distribution, cfg: DrawConfig, lazy: bool = False) -> tor
         _DIRICHLET_DRAWS += 1
         x = _DirichletRsampleFn.apply(cfg, conc)
         return x.reshape((cfg.K,) + tuple(distribution.batch_shape) + (C,))
+    if native_lowrank(distribution):
+        # the public loc and the unbroadcast cov_factor / cov_diag (of an unbatched factor: the
+        # constructor's own arguments, which carry the autograd of the parameterisation)
+        global _LOWRANK_DRAWS
+        cov_factor = distribution._unbroadcasted_cov_factor
+        cov_diag = distribution._unbroadcasted_cov_diag
+        fill_exp(cov_diag)
+        D, R = (int(n) for n in cov_factor.shape)
+        loc = distribution.loc.reshape(D).contiguous()
+        if cfg.noise is not None:   # injected eps_D | eps_W, [K, D + R]
+            cfg.noise = cfg.noise.to(device=loc.device, dtype=torch.float32) \
+                .reshape(cfg.K, D + R).contiguous()
+        _LOWRANK_DRAWS += 1
+        return _LowRankRsampleFn.apply(cfg, loc, cov_factor.contiguous(), cov_diag.contiguous())
     if cfg.noise is not None:
         return cfg.noise
     return distribution.rsample(torch.Size([cfg.K]))
@@ -876,10 +968,10 @@ def draw_all(approximation: Dict[str, Distribution], K: int, seed: int, step: in
     Normal factors become :class:`LazyDraw` placeholders evaluated inside the site kernels.
     ``element_offsets``: global index of element 0 of data-sharded factors (multiples of 4).
     """
-    global _MVN_DRAWS, _DIRICHLET_DRAWS
+    global _MVN_DRAWS, _DIRICHLET_DRAWS, _LOWRANK_DRAWS
     _LAZY.clear()
     _DRAWN.clear()
-    _MVN_DRAWS = _DIRICHLET_DRAWS = 0
+    _MVN_DRAWS = _DIRICHLET_DRAWS = _LOWRANK_DRAWS = 0
     flush_draws(claimed=True)
     samples = {}
     for stream_id, (name, factor) in enumerate(approximation.items()):

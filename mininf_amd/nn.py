@@ -123,7 +123,13 @@ class ParameterizedDistribution(nn.Module):
                     arguments[name] = forward(unconstrained)
                 if isinstance(forward, distributions.ExpTransform):
                     sources[name] = (unconstrained, "exp")
-        distribution = _construct(self.distribution_cls, arguments, self.distribution_constants)
+        if _native_lowrank_arguments(self.distribution_cls, arguments):
+            with _CapturableCholesky():
+                distribution = _construct(self.distribution_cls, arguments,
+                                          self.distribution_constants)
+        else:
+            distribution = _construct(self.distribution_cls, arguments,
+                                      self.distribution_constants)
         # How each parameter derives from this module's nn.Parameters: the fused ELBO can then
         # write the guide's gradients directly (mi_factor transforms, engine.elbo).
         distribution._mininf_amd_sources = sources  # type: ignore[attr-defined]
@@ -167,6 +173,36 @@ class ParameterizedDistribution(nn.Module):
         beta._mininf_amd_sources = {  # type: ignore[attr-defined]
             "concentration1": (u1, "exp"), "concentration0": (u0, "exp")}
         return beta
+
+
+def _native_lowrank_arguments(cls, arguments: Dict) -> bool:
+    """Whether ``cls(**arguments)`` is a LowRankMultivariateNormal the native sampler draws
+    (guide.native_lowrank): unbatched, float32, on the device, rank within the cap."""
+    if cls is not distributions.LowRankMultivariateNormal or \
+            set(arguments) != {"loc", "cov_factor", "cov_diag"}:
+        return False
+    loc, factor, diag = (arguments[name] for name in ("loc", "cov_factor", "cov_diag"))
+    return all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32
+               for t in (loc, factor, diag)) and \
+        loc.dim() == 1 and factor.dim() == 2 and diag.dim() == 1 and \
+        1 <= factor.shape[-1] <= _native.LOWRANK_MAX_R
+
+
+class _CapturableCholesky(torch.overrides.TorchFunctionMode):
+    """
+    Sends the ``torch.linalg.cholesky`` of LowRankMultivariateNormal's constructor
+    (lowrank_multivariate_normal.py:17-26, the R x R capacitance matrix) to ``mvn.cholesky_ex``:
+    mi_cholesky with torch's backward, no host synchronisation, so a captured step can hold it
+    (rocSOLVER's potrf cannot be captured). The returned ``info`` is not read: the capacitance
+    matrix I + W^T diag(1 / d) W is positive definite whenever cov_diag > 0, which the argument
+    validation checks (and ParameterizedDistribution's exp transform guarantees).
+    """
+    def __torch_function__(self, func, types, args=(), kwargs=None):
+        from . import mvn
+        if func is torch.linalg.cholesky and not kwargs and len(args) == 1 and \
+                mvn.cholesky_supported(args[0]):
+            return mvn.cholesky_ex(args[0])[0]
+        return func(*args, **(kwargs or {}))
 
 
 # Guide families whose constructor builds no inner distribution: their argument validation can
@@ -430,14 +466,16 @@ class EvidenceLowerBoundLoss(nn.Module):
             sharded factors draw their slice of the global draw.
 
     Guide factors of type Normal, Beta, Gamma, MultivariateNormal (unbatched, float32, on the
-    device, at most 1024 dimensions; any of its three parameterisations) and Dirichlet (float32, on
-    the device, at most 1024 categories) are drawn by the native samplers: ``seed`` governs their
-    draws, particle shards draw the union of what one device would draw, and a captured step draws
-    anew on every replay. Their entropy is evaluated inside the ELBO kernels (Dirichlet: by its own
-    kernel, ``mi_dirichlet_entropy``). Every other factor uses its own ``rsample`` (torch's
-    generator) and ``entropy``. ``last_fusions`` reports the fast paths the last evaluation took,
-    among them ``mvn_draws`` and ``dirichlet_draws``, the numbers of factors the native
-    MultivariateNormal and Dirichlet samplers drew.
+    device, at most 1024 dimensions; any of its three parameterisations), Dirichlet (float32, on
+    the device, at most 1024 categories) and LowRankMultivariateNormal (unbatched, float32, on the
+    device, rank at most 128, at most 2**24 dimensions) are drawn by the native samplers: ``seed``
+    governs their draws, particle shards draw the union of what one device would draw, and a
+    captured step draws anew on every replay. Their entropy is evaluated inside the ELBO kernels
+    (Dirichlet: by its own kernel, ``mi_dirichlet_entropy``; LowRankMultivariateNormal: by torch's
+    own ``entropy``). Every other factor uses its own ``rsample`` (torch's generator) and
+    ``entropy``. ``last_fusions`` reports the fast paths the last evaluation took, among them
+    ``mvn_draws``, ``dirichlet_draws`` and ``lowrank_draws``, the numbers of factors the native
+    MultivariateNormal, Dirichlet and LowRankMultivariateNormal samplers drew.
 
     Example:
 
