@@ -1,13 +1,14 @@
 """
 In-tree build of ``libmininf_amd.so`` (gfx950). Used by ``__graft_entry__.build()`` and the tests.
 
-The library holds the precompiled kernels (sites.hip, guide.hip, mvn_guide.hip, lowrank_guide.hip, dirichlet.hip, elbo.hip, linear.hip) and the host-side site-program
-specialiser (jit.cpp), which embeds ``include/mininf_amd.h`` and ``csrc/device_math.hpp`` verbatim
+The library holds the precompiled kernels (every ``csrc/*.hip`` in ``SOURCES``) and the host-side
+site-program specialiser (jit.cpp), which embeds ``include/mininf_amd.h`` and ``csrc/device_math.hpp`` verbatim
 so that kernels compiled at trace time by hiprtc share the exact device math of the precompiled
 ones.
 """
 from __future__ import annotations
 
+import glob
 import os
 import subprocess
 import sys
@@ -20,10 +21,8 @@ SOURCES = [os.path.join(CSRC, name)
            for name in ("sites.hip", "guide.hip", "elbo.hip", "linear.hip", "minibatch.hip",
                         "adam.hip", "mvn.hip", "mvn_guide.hip", "lowrank_guide.hip", "dirichlet.hip",
                         "peer.hip", "jit.cpp")]
-HEADERS = [os.path.join(CSRC, name) for name in ("common.hpp", "device_math.hpp", "beta_grad.hpp",
-                                                 "gamma_sample.hpp", "jit.hpp",
-                                                 "internal.hpp", "entropy.hpp", "adam_math.hpp")] + \
-    [os.path.join(INCLUDE, "mininf_amd.h")]
+# every header: a change to any of them rebuilds every object
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + [os.path.join(INCLUDE, "mininf_amd.h")]
 EMBEDDED = {"embedded_header.inc": os.path.join(INCLUDE, "mininf_amd.h"),
             "embedded_math.inc": os.path.join(CSRC, "device_math.hpp")}
 TARGET = os.path.join(HERE, "libmininf_amd.so")

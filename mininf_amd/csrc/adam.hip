@@ -292,12 +292,6 @@ __global__ __launch_bounds__(kAdamBlock) void k_adam_step(const mi_adam A, const
 
 }  // namespace mi
 
-namespace {
-
-int to_code(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
-
-}  // namespace
-
 extern "C" {
 
 int mi_adam_step(const mi_adam* adam, uint32_t* counters, void* stream) {

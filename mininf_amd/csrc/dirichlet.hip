@@ -14,6 +14,7 @@
 // so results do not depend on the launch.
 #include "beta_grad.hpp"
 #include "gamma_sample.hpp"
+#include "internal.hpp"
 
 #include <algorithm>
 
@@ -317,9 +318,6 @@ __global__ __launch_bounds__(kDirThreads) void k_dirichlet_entropy(
 
 namespace {
 
-int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-int to_code(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
-
 // Lanes per row: min(64, next_pow2(C)), and its log2.
 void row_group(int64_t C, int* W, int* shift) {
   int w = 1, s = 0;
@@ -335,32 +333,11 @@ void row_group(int64_t C, int* W, int* shift) {
 int64_t row_blocks(int64_t rows, int W) {
   const int64_t waves = ceil_div(rows, 64 / W);
   const int64_t blocks = ceil_div(waves, mi::kDirThreads / 64);
-  return blocks <= 0x7FFFFFFF ? blocks : 0;
+  return blocks <= kMaxGrid ? blocks : 0;
 }
 
 bool shape_ok(int64_t K, int64_t N, int64_t C) {
   return K >= 1 && N >= 1 && C >= 1 && K <= (INT64_MAX / 8) / N && K * N <= (INT64_MAX / 8) / C;
-}
-
-// Particle slices of the sampler's backward (elements N C, as bwd_geometry of guide.hip).
-struct BwdGeometry {
-  int ti;
-  int64_t gx, slices, rows;
-};
-
-BwdGeometry bwd_geometry(int64_t K, int64_t units) {
-  BwdGeometry g{};
-  int ti = 1;
-  while (ti < 64 && ti < units) ti <<= 1;
-  g.ti = ti;
-  const int tk = mi::kDirThreads / ti;
-  g.gx = ceil_div(units, ti);
-  int64_t slices = ceil_div(1024, g.gx);
-  slices = std::min<int64_t>(slices, ceil_div(K, (int64_t)tk * 2));
-  slices = std::max<int64_t>(1, slices);
-  g.rows = ceil_div(K, slices);
-  g.slices = ceil_div(K, g.rows);
-  return g;
 }
 
 size_t align8(size_t n) { return (n + 7) & ~(size_t)7; }
@@ -430,7 +407,7 @@ int mi_dirichlet_rsample_backward_workspace_bytes(int64_t K, int64_t N, int64_t 
                                                   size_t* bytes) {
   if (!shape_ok(K, N, C) || bytes == nullptr) return MI_EINVAL;
   if (C > MI_DIRICHLET_MAX_C) return MI_EUNSUPPORTED;
-  const BwdGeometry geo = bwd_geometry(K, N * C);
+  const BwdGeometry geo = bwd_geometry(K, N * C, mi::kDirThreads);
   // dot [K, N] and psi_tot [N] (fp64), tot [N] (fp32), then the slices' partial sums
   *bytes = (size_t)K * N * sizeof(double) + (size_t)N * sizeof(double) +
            align8((size_t)N * sizeof(float)) +
@@ -448,12 +425,12 @@ int mi_dirichlet_rsample_backward(const float* dx, int64_t dx_stride_k, int64_t 
   if (C > MI_DIRICHLET_MAX_C) return MI_EUNSUPPORTED;
   size_t need = 0;
   mi_dirichlet_rsample_backward_workspace_bytes(K, N, C, &need);
-  if (workspace == nullptr || workspace_bytes < need) return MI_EWORKSPACE;
+  if (!workspace_ok(workspace, workspace_bytes, need)) return MI_EWORKSPACE;
   int W, shift;
   row_group(C, &W, &shift);
   const int64_t blocks = row_blocks(K * N, W);
-  const BwdGeometry geo = bwd_geometry(K, N * C);
-  if (blocks == 0 || geo.gx > 0x7FFFFFFF) return MI_EUNSUPPORTED;
+  const BwdGeometry geo = bwd_geometry(K, N * C, mi::kDirThreads);
+  if (blocks == 0 || geo.gx > kMaxGrid) return MI_EUNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
   char* base = static_cast<char*>(workspace);
   double* dot = reinterpret_cast<double*>(base);
@@ -461,12 +438,12 @@ int mi_dirichlet_rsample_backward(const float* dx, int64_t dx_stride_k, int64_t 
   float* tot = reinterpret_cast<float*>(psi_tot + N);
   float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(tot) +
                                          align8((size_t)N * sizeof(float)));
+  float* out = slice_out(dconcentration, part, geo.slices, 0);
   hipLaunchKernelGGL(mi::k_dirichlet_bwd_dot, dim3((unsigned)blocks), dim3(mi::kDirThreads), 0, s,
                      dx, dx_stride_k, dx_stride_i, dx_stride_c, x, concentration, K, N, C, dot,
                      tot, psi_tot, W, shift);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return to_code(e);
-  float* out = geo.slices > 1 ? part : dconcentration;
   hipLaunchKernelGGL(mi::k_dirichlet_rsample_bwd, dim3((unsigned)geo.gx, (unsigned)geo.slices),
                      dim3(mi::kDirThreads), 0, s, dx, dx_stride_k, dx_stride_i, dx_stride_c, x,
                      concentration, dot, tot, psi_tot, K, N, C, out, geo.rows, geo.ti);

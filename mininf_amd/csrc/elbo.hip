@@ -1470,8 +1470,6 @@ __global__ __launch_bounds__(kElboThreads) void k_elbo_backward(const mi_elbo E,
 
 namespace {
 
-int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 bool valid_factor(const mi_factor& F) {
   if (!(F.weight > 0.0) || !std::isfinite(F.weight) || F.element_offset < 0 ||
       (F.element_offset & 3) != 0)
@@ -1821,8 +1819,6 @@ bool final_complete(const mi_elbo* e, const Layout& L) {
 size_t workspace_need(const mi_elbo* e) {
   return MI_ELBO_COUNTER_BYTES + sizeof(double) * (size_t)make_layout(e).doubles;
 }
-
-int to_code(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 
 }  // namespace
 

@@ -11,6 +11,7 @@
 // Philox counter (seed, step, stream, global particle, element quad).
 #include "beta_grad.hpp"
 #include "gamma_sample.hpp"
+#include "internal.hpp"
 
 #include <algorithm>
 
@@ -382,35 +383,6 @@ __global__ void k_philox_raw(const uint32_t* __restrict__ ctr, int64_t count, ui
 
 }  // namespace mi
 
-namespace {
-
-int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-int to_code(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
-
-// Launch geometry of the particle-reducing backward kernels: `lanes` element lanes per block
-// (TI), 256 / TI particle lanes, and enough particle slices to fill the chip.
-struct BwdGeometry {
-  int ti;
-  int64_t gx, slices, rows;
-};
-
-BwdGeometry bwd_geometry(int64_t K, int64_t units) {
-  BwdGeometry g{};
-  int ti = 1;
-  while (ti < 64 && ti < units) ti <<= 1;
-  g.ti = ti;
-  const int tk = 256 / ti;
-  g.gx = ceil_div(units, ti);
-  int64_t slices = ceil_div(1024, g.gx);
-  slices = std::min<int64_t>(slices, ceil_div(K, (int64_t)tk * 2));
-  slices = std::max<int64_t>(1, slices);
-  g.rows = ceil_div(K, slices);
-  g.slices = ceil_div(K, g.rows);
-  return g;
-}
-
-}  // namespace
-
 extern "C" {
 
 int mi_normal_rsample(const float* loc, int64_t loc_stride, const float* scale, int64_t scale_stride,
@@ -449,7 +421,7 @@ int mi_normal_rsample_exp(const float* loc, int64_t loc_stride, const float* u, 
 
 int mi_normal_rsample_backward_workspace_bytes(int64_t K, int64_t N, size_t* bytes) {
   if (K < 1 || N < 1 || bytes == nullptr) return MI_EINVAL;
-  const BwdGeometry geo = bwd_geometry(K, ceil_div(N, 4));
+  const BwdGeometry geo = bwd_geometry(K, ceil_div(N, 4), mi::kGuideThreads);
   *bytes = geo.slices > 1 ? (size_t)geo.slices * 2 * (size_t)N * sizeof(float) : 0;
   return 0;
 }
@@ -465,16 +437,12 @@ int mi_normal_rsample_backward(const float* dz, int64_t dz_stride_k, int64_t dz_
     return MI_EINVAL;
   size_t need = 0;
   mi_normal_rsample_backward_workspace_bytes(K, N, &need);
-  if (need > 0 && (workspace == nullptr || workspace_bytes < need)) return MI_EWORKSPACE;
+  if (!workspace_ok(workspace, workspace_bytes, need)) return MI_EWORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const BwdGeometry geo = bwd_geometry(K, ceil_div(N, 4));
+  const BwdGeometry geo = bwd_geometry(K, ceil_div(N, 4), mi::kGuideThreads);
   const int64_t rows = geo.rows, gy = geo.slices, gx = geo.gx;
-  float* out_loc = dloc;
-  float* out_scale = dscale;
-  if (gy > 1) {
-    out_loc = static_cast<float*>(workspace);
-    out_scale = out_loc + gy * N;
-  }
+  float* out_loc = slice_out(dloc, workspace, gy, 0);
+  float* out_scale = slice_out(dscale, workspace, gy, gy * N);
   hipLaunchKernelGGL(mi::k_normal_rsample_bwd, dim3((unsigned)gx, (unsigned)gy),
                      dim3(mi::kGuideThreads), 0, s, dz, dz_stride_k, dz_stride_i, K, N, seed, step,
                      step_device, stream_id, particle_offset, element_offset >> 2, eps, out_loc,
@@ -516,7 +484,7 @@ int mi_beta_rsample_exp(const float* u1, int64_t u1_stride, const float* u0, int
 
 int mi_beta_rsample_backward_workspace_bytes(int64_t K, int64_t N, size_t* bytes) {
   if (K < 1 || N < 1 || bytes == nullptr) return MI_EINVAL;
-  const BwdGeometry geo = bwd_geometry(K, N);
+  const BwdGeometry geo = bwd_geometry(K, N, mi::kGuideThreads);
   *bytes = geo.slices > 1 ? (size_t)geo.slices * 2 * (size_t)N * sizeof(float) : 0;
   return 0;
 }
@@ -531,18 +499,13 @@ int mi_beta_rsample_backward(const float* dx, int64_t dx_stride_k, int64_t dx_st
     return MI_EINVAL;
   size_t need = 0;
   mi_beta_rsample_backward_workspace_bytes(K, N, &need);
-  if (need > 0 && (workspace == nullptr || workspace_bytes < need)) return MI_EWORKSPACE;
+  if (!workspace_ok(workspace, workspace_bytes, need)) return MI_EWORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const BwdGeometry geo = bwd_geometry(K, N);
+  const BwdGeometry geo = bwd_geometry(K, N, mi::kGuideThreads);
   const int64_t rows = geo.rows, gy = geo.slices;
-  float* o1 = dc1;
-  float* o0 = dc0;
-  int64_t s1 = dc1_stride, s0 = dc0_stride;
-  if (gy > 1) {
-    o1 = static_cast<float*>(workspace);
-    o0 = o1 + gy * N;
-    s1 = s0 = 1;
-  }
+  float* o1 = slice_out(dc1, workspace, gy, 0);
+  float* o0 = slice_out(dc0, workspace, gy, gy * N);
+  const int64_t s1 = gy > 1 ? 1 : dc1_stride, s0 = gy > 1 ? 1 : dc0_stride;
   hipLaunchKernelGGL(mi::k_beta_rsample_bwd, dim3((unsigned)geo.gx, (unsigned)gy),
                      dim3(mi::kGuideThreads), 0, s, dx, dx_stride_k, dx_stride_i, x, c1, c1_stride,
                      c0, c0_stride, K, N, o1, s1, o0, s0, N, rows, geo.ti);
@@ -584,18 +547,13 @@ int mi_gamma_rsample_backward(const float* dx, int64_t dx_stride_k, int64_t dx_s
     return MI_EINVAL;
   size_t need = 0;
   mi_gamma_rsample_backward_workspace_bytes(K, N, &need);
-  if (need > 0 && (workspace == nullptr || workspace_bytes < need)) return MI_EWORKSPACE;
+  if (!workspace_ok(workspace, workspace_bytes, need)) return MI_EWORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const BwdGeometry geo = bwd_geometry(K, N);
+  const BwdGeometry geo = bwd_geometry(K, N, mi::kGuideThreads);
   const int64_t rows = geo.rows, gy = geo.slices;
-  float* oc = dconcentration;
-  float* orr = drate;
-  int64_t sc = dconcentration_stride, sr = drate_stride;
-  if (gy > 1) {
-    oc = static_cast<float*>(workspace);
-    orr = oc + gy * N;
-    sc = sr = 1;
-  }
+  float* oc = slice_out(dconcentration, workspace, gy, 0);
+  float* orr = slice_out(drate, workspace, gy, gy * N);
+  const int64_t sc = gy > 1 ? 1 : dconcentration_stride, sr = gy > 1 ? 1 : drate_stride;
   hipLaunchKernelGGL(mi::k_gamma_rsample_bwd, dim3((unsigned)geo.gx, (unsigned)gy),
                      dim3(mi::kGuideThreads), 0, s, dx, dx_stride_k, dx_stride_i, g, concentration,
                      concentration_stride, rate, rate_stride, K, N, oc, sc, orr, sr, N, rows,

@@ -3,8 +3,48 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
+
+inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+inline int to_code(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
+
+constexpr int64_t kMaxGrid = 0x7FFFFFFF;   // blocks along x of a grid
+
+// Launch geometry of the particle-reducing sampler backwards (guide.hip, dirichlet.hip): blocks of
+// `threads`, `ti` element lanes (min(64, next_pow2(units))) x threads / ti particle lanes, and
+// enough particle slices of `rows` particles to fill the chip.
+struct BwdGeometry {
+  int ti;
+  int64_t gx, slices, rows;
+};
+
+inline BwdGeometry bwd_geometry(int64_t K, int64_t units, int threads) {
+  BwdGeometry g{};
+  int ti = 1;
+  while (ti < 64 && ti < units) ti <<= 1;
+  g.ti = ti;
+  const int tk = threads / ti;
+  g.gx = ceil_div(units, ti);
+  int64_t slices = ceil_div(1024, g.gx);
+  slices = std::min<int64_t>(slices, ceil_div(K, (int64_t)tk * 2));
+  slices = std::max<int64_t>(1, slices);
+  g.rows = ceil_div(K, slices);
+  g.slices = ceil_div(K, g.rows);
+  return g;
+}
+
+// The tail every sliced sampler backward shares. A workspace of `need` bytes was asked for (none:
+// any pointer does) ...
+inline bool workspace_ok(const void* workspace, size_t bytes, size_t need) {
+  return need == 0 || (workspace != nullptr && bytes >= need);
+}
+// ... and with more than one particle slice the kernel writes per-slice partials at float
+// `offset` of the workspace instead of the output itself (a slice-summing launch follows).
+inline float* slice_out(float* out, void* workspace, int64_t slices, int64_t offset) {
+  return slices > 1 ? static_cast<float*>(workspace) + offset : out;
+}
 
 // Fixed-order fp64 reduction of per-(segment, particle) partials part[v][nseg][K] (sites.hip
 // k_finalize): values v < num_sites are multiplied by scale[v] and summed into total[k] (and

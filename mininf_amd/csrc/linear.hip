@@ -757,8 +757,6 @@ __global__ __launch_bounds__(NT, MINW) void k_linear_mfma(const mi_linear L, int
 
 namespace {
 
-int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 bool valid(const mi_linear* L) {
   if (L != nullptr && L->rows.counter != nullptr) {
     const mi_rows& R = L->rows;   // mi_minibatch_rows's conditions
@@ -848,8 +846,6 @@ Geometry geometry(const mi_linear* L) {
   g.gx = g.ntile;
   return g;
 }
-
-int to_code(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 
 // The launch conditions of the site's options on this geometry (shared by the plain and the
 // ELBO-finishing forward): 0, MI_EUNSUPPORTED or MI_EINVAL.

@@ -52,12 +52,6 @@ __global__ __launch_bounds__(256) void k_gather_rows(const uint32_t* __restrict_
 
 }  // namespace mi
 
-namespace {
-
-int to_code(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
-
-}  // namespace
-
 extern "C" {
 
 int mi_minibatch_rows(uint64_t* counter, int64_t n, int64_t batch, int64_t batches_per_epoch,

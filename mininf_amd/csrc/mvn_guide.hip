@@ -18,74 +18,48 @@
 // Every z[k, i] is the chain acc = loc[i]; acc = fma(eps[k, j], L[i, j], acc) for j ascending (an
 // f32 MFMA is exactly that chain), whichever tile row the particle falls in: a draw does not depend
 // on particle_offset or on K. D < 32 runs the same chain on the VALU.
-#include "common.hpp"
+#include "internal.hpp"
+#include "mfma_tile.hpp"
 
 #include <algorithm>
 
 namespace mi {
 
-typedef float mvn_f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kMvnThreads = 256;
-constexpr int kMvnTile = 32;
-constexpr int kMvnStride = kMvnTile + 1;   // LDS row stride: column and row reads both conflict-free
-constexpr int kMvnWaves = kMvnThreads / kWave;
-
-// Stage the eps tile of particles [kbase, kbase + 32) x elements [32 jt, 32 jt + 32) into
-// es[particle][element]: one element quad per thread (zero outside K x D).
-MI_DEV void mvn_stage_eps(float* __restrict__ es, int64_t kbase, int jt, int64_t K, int64_t D,
-                          uint64_t seed, uint64_t step, uint32_t stream_id, int64_t poff,
-                          const float* __restrict__ eps_in) {
-  const int q = threadIdx.x & 7, p = threadIdx.x >> 3;
-  const int64_t k = kbase + p;
-  const int64_t j0 = (int64_t)jt * kMvnTile + 4 * q;
-  float e[4] = {0.f, 0.f, 0.f, 0.f};
-  if (k < K && j0 < D) {
-    if (eps_in != nullptr) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) e[c] = (j0 + c < D) ? eps_in[k * D + j0 + c] : 0.0f;
-    } else {
-      guide_normals(seed, step, stream_id, (uint64_t)(j0 >> 2), (uint64_t)(poff + k), e);
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < 4; ++c) es[p * kMvnStride + 4 * q + c] = (j0 + c < D) ? e[c] : 0.0f;
-}
-
-// The C/D row of accumulator register r (32x32 MFMA: the column is lane & 31).
-MI_DEV int mvn_acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
+constexpr int kMvnThreads = 256;   // the VALU kernels and the slice combination
 
 // ---- forward, D >= 32 ------------------------------------------------------------------------
-__global__ __launch_bounds__(kMvnThreads) void k_mvn_rsample_mfma(
+__global__ __launch_bounds__(kTileThreads) void k_mvn_rsample_mfma(
     const float* __restrict__ loc, const float* __restrict__ L, int64_t K, int64_t D,
     uint64_t seed, uint64_t step, const uint64_t* __restrict__ step_dev, uint32_t stream_id,
     int64_t poff, const float* __restrict__ eps_in, float* __restrict__ z) {
-  __shared__ float es[kMvnTile * kMvnStride];
-  __shared__ float ls[kMvnWaves][kMvnTile * kMvnStride];
+  __shared__ float es[kTileFloats];
+  __shared__ float ls[kTileWaves][kTileFloats];
   if (step_dev != nullptr) step += *step_dev;
   const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
   const int col = lane & 31, half = lane >> 5;
-  const int T = (int)((D + kMvnTile - 1) / kMvnTile);
+  const int T = (int)((D + kTile - 1) / kTile);
   // the longest chains (the last element tiles) start first
   const int group = (int)(gridDim.y - 1 - blockIdx.y);
-  const int it = group * kMvnWaves + w;
+  const int it = group * kTileWaves + w;
   const bool active = it < T;
-  const int jt_last = min(T - 1, group * kMvnWaves + kMvnWaves - 1);
-  const int64_t kbase = (int64_t)blockIdx.x * kMvnTile;
-  const int64_t ibase = (int64_t)it * kMvnTile;
+  const int jt_last = min(T - 1, group * kTileWaves + kTileWaves - 1);
+  const int64_t kbase = (int64_t)blockIdx.x * kTile;
+  const int64_t ibase = (int64_t)it * kTile;
+  const NormalsKey key{seed, step, stream_id, poff, eps_in, D};
+  const NormalsSection sec{D, 0, 0};   // eps: the whole stream of the factor
 
   // L[ibase + 2 r + half, 32 jt + col] for r = 0 .. 15, zero above the diagonal and outside D
   // (the strict upper triangle is never read)
   float lreg[16];
   auto load_l = [&](int jt) {
-    const int64_t j = (int64_t)jt * kMvnTile + col;
+    const int64_t j = (int64_t)jt * kTile + col;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int64_t i = ibase + 2 * r + half;
       lreg[r] = (i < D && j <= i) ? L[i * D + j] : 0.0f;
     }
   };
-  mvn_f32x16 acc;
+  f32x16 acc;
   {
     const int64_t i = ibase + col;
     const float m = (active && i < D) ? loc[i] : 0.0f;
@@ -97,19 +71,12 @@ __global__ __launch_bounds__(kMvnThreads) void k_mvn_rsample_mfma(
     const bool mine = active && jt <= it;
     if (mine) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) ls[w][(2 * r + half) * kMvnStride + col] = lreg[r];
+      for (int r = 0; r < 16; ++r) ls[w][(2 * r + half) * kTileStride + col] = lreg[r];
     }
-    mvn_stage_eps(es, kbase, jt, K, D, seed, step, stream_id, poff, eps_in);
+    stage_tile<kTileThreads>(es, key, sec, kbase, K, (int64_t)jt * kTile, threadIdx.x);
     __syncthreads();
     if (active && jt + 1 <= it) load_l(jt + 1);   // in flight behind the MFMAs
-    if (mine) {
-#pragma unroll
-      for (int s = 0; s < 16; ++s) {
-        const float a = es[col * kMvnStride + 2 * s + half];      // A[particle][j]
-        const float b = ls[w][col * kMvnStride + 2 * s + half];   // B[j][i] = L[i][j]
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-      }
-    }
+    if (mine) mfma_tile_nt(acc, es, ls[w], lane);   // A[particle][j], B[j][i] = L[i][j]
     __syncthreads();
   }
   if (!active) return;
@@ -117,7 +84,7 @@ __global__ __launch_bounds__(kMvnThreads) void k_mvn_rsample_mfma(
   if (i >= D) return;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int64_t k = kbase + mvn_acc_row(r, lane);
+    const int64_t k = kbase + acc_row(r, lane);
     if (k < K) z[k * D + i] = acc[r];
   }
 }
@@ -150,54 +117,50 @@ __global__ __launch_bounds__(kMvnThreads) void k_mvn_rsample_valu(
 // ---- backward, D >= 32 -----------------------------------------------------------------------
 // grid (j tile, group of four i tiles, particle slice). out_l / out_loc: the outputs themselves
 // (one slice) or this slice's [D * D] / [D] partials.
-__global__ __launch_bounds__(kMvnThreads) void k_mvn_rsample_bwd_mfma(
+__global__ __launch_bounds__(kTileThreads) void k_mvn_rsample_bwd_mfma(
     const float* __restrict__ dz, int64_t dz_sk, int64_t dz_si, int64_t K, int64_t D,
     uint64_t seed, uint64_t step, const uint64_t* __restrict__ step_dev, uint32_t stream_id,
     int64_t poff, const float* __restrict__ eps_in, int tiles_per_slice, int64_t slice_stride,
     float* __restrict__ out_loc, float* __restrict__ out_l) {
-  __shared__ float es[kMvnTile * kMvnStride];
-  __shared__ float ds[kMvnWaves][kMvnTile * kMvnStride];
+  __shared__ float es[kTileFloats];
+  __shared__ float ds[kTileWaves][kTileFloats];
   if (step_dev != nullptr) step += *step_dev;
   const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
   const int col = lane & 31, half = lane >> 5;
-  const int T = (int)((D + kMvnTile - 1) / kMvnTile);
+  const int T = (int)((D + kTile - 1) / kTile);
   const int jt = blockIdx.x;
-  const int it = (int)blockIdx.y * kMvnWaves + w;
+  const int it = (int)blockIdx.y * kTileWaves + w;
   const bool single = gridDim.z == 1;
-  const int64_t ibase = (int64_t)it * kMvnTile, jbase = (int64_t)jt * kMvnTile;
+  const int64_t ibase = (int64_t)it * kTile, jbase = (int64_t)jt * kTile;
   float* __restrict__ dst_l = out_l + (int64_t)blockIdx.z * slice_stride;
   float* __restrict__ dst_loc = out_loc + (int64_t)blockIdx.z * D;
   const bool lower = it < T && jt <= it;   // this wave's tile holds entries of the lower triangle
   // no wave of the block has such a tile: nothing to sum (block-uniform)
-  const bool any_lower = (int)blockIdx.y * kMvnWaves + kMvnWaves - 1 >= jt;
-  mvn_f32x16 acc;
+  const bool any_lower = (int)blockIdx.y * kTileWaves + kTileWaves - 1 >= jt;
+  const NormalsKey key{seed, step, stream_id, poff, eps_in, D};
+  const NormalsSection sec{D, 0, 0};   // eps: the whole stream of the factor
+  f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
   float sum_loc = 0.0f;
   if (any_lower) {
-    const int64_t nkt = (K + kMvnTile - 1) / kMvnTile;
+    const int64_t nkt = (K + kTile - 1) / kTile;
     const int64_t kt0 = (int64_t)blockIdx.z * tiles_per_slice;
     const int64_t kt1 = min(nkt, kt0 + tiles_per_slice);
-    // lanes run along the unit-stride axis of dz
-    const bool along_i = dz_si == 1 || dz_sk != 1;
     for (int64_t kt = kt0; kt < kt1; ++kt) {
-      const int64_t kbase = kt * kMvnTile;
+      const int64_t kbase = kt * kTile;
       if (lower) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int kk = along_i ? 2 * r + half : col;
-          const int ii = along_i ? col : 2 * r + half;
-          const int64_t k = kbase + kk, i = ibase + ii;
-          ds[w][kk * kMvnStride + ii] = (k < K && i < D) ? dz[k * dz_sk + i * dz_si] : 0.0f;
-        }
+        for (int r = 0; r < 16; ++r)
+          stage_dz_row(ds[w], dz, dz_sk, dz_si, kbase, K, ibase, D, r, lane);
       }
-      mvn_stage_eps(es, kbase, jt, K, D, seed, step, stream_id, poff, eps_in);
+      stage_tile<kTileThreads>(es, key, sec, kbase, K, jbase, threadIdx.x);
       __syncthreads();
       if (lower) {
 #pragma unroll
         for (int s = 0; s < 16; ++s) {
-          const float a = ds[w][(2 * s + half) * kMvnStride + col];   // A[i][k] = dz[k][i]
-          const float b = es[(2 * s + half) * kMvnStride + col];      // B[k][j] = eps[k][j]
+          const float a = tile_k_major(ds[w], s, lane);   // A[i][k] = dz[k][i]
+          const float b = tile_k_major(es, s, lane);      // B[k][j] = eps[k][j]
           sum_loc += a;
           acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
         }
@@ -211,7 +174,7 @@ __global__ __launch_bounds__(kMvnThreads) void k_mvn_rsample_bwd_mfma(
   if (j < D) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int64_t i = ibase + mvn_acc_row(r, lane);
+      const int64_t i = ibase + acc_row(r, lane);
       if (i < D) dst_l[i * D + j] = (lower && j <= i) ? acc[r] : 0.0f;
     }
   }
@@ -286,9 +249,6 @@ __global__ __launch_bounds__(kMvnThreads) void k_mvn_sum_slices(const float* __r
 
 namespace {
 
-int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-int to_code(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
-
 int check_shape(int64_t K, int64_t D) {
   if (K < 1 || D < 1) return MI_EINVAL;
   if (D > MI_MVN_MAX_N) return MI_EUNSUPPORTED;
@@ -306,11 +266,11 @@ struct MvnBwdGeometry {
 
 MvnBwdGeometry mvn_bwd_geometry(int64_t K, int64_t D) {
   MvnBwdGeometry g{};
-  g.mfma = D >= mi::kMvnTile;
+  g.mfma = D >= mi::kTile;
   if (g.mfma) {
-    g.tiles = ceil_div(D, mi::kMvnTile);
+    g.tiles = ceil_div(D, mi::kTile);
     const int64_t lower = g.tiles * (g.tiles + 1) / 2;
-    const int64_t nkt = ceil_div(K, mi::kMvnTile);
+    const int64_t nkt = ceil_div(K, mi::kTile);
     const int64_t want = std::max<int64_t>(1, std::min<int64_t>(nkt, ceil_div(512, lower)));
     g.per = ceil_div(nkt, want);
     g.slices = ceil_div(nkt, g.per);
@@ -333,10 +293,10 @@ int mi_mvn_rsample(const float* loc, const float* scale_tril, int64_t K, int64_t
   if (loc == nullptr || scale_tril == nullptr || z == nullptr || stream_id > 0xFFFFFFu)
     return MI_EINVAL;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (D >= mi::kMvnTile) {
-    const dim3 grid((unsigned)ceil_div(K, mi::kMvnTile),
-                    (unsigned)ceil_div(ceil_div(D, mi::kMvnTile), mi::kMvnWaves));
-    hipLaunchKernelGGL(mi::k_mvn_rsample_mfma, grid, dim3(mi::kMvnThreads), 0, s, loc, scale_tril,
+  if (D >= mi::kTile) {
+    const dim3 grid((unsigned)ceil_div(K, mi::kTile),
+                    (unsigned)ceil_div(ceil_div(D, mi::kTile), mi::kTileWaves));
+    hipLaunchKernelGGL(mi::k_mvn_rsample_mfma, grid, dim3(mi::kTileThreads), 0, s, loc, scale_tril,
                        K, D, seed, step, step_device, stream_id, particle_offset, eps, z);
   } else {
     hipLaunchKernelGGL(mi::k_mvn_rsample_valu, dim3((unsigned)ceil_div(K * D, mi::kMvnThreads)),
@@ -366,19 +326,15 @@ int mi_mvn_rsample_backward(const float* dz, int64_t dz_stride_k, int64_t dz_str
     return MI_EINVAL;
   size_t need = 0;
   mi_mvn_rsample_backward_workspace_bytes(K, D, &need);
-  if (need > 0 && (workspace == nullptr || workspace_bytes < need)) return MI_EWORKSPACE;
+  if (!workspace_ok(workspace, workspace_bytes, need)) return MI_EWORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const MvnBwdGeometry g = mvn_bwd_geometry(K, D);
-  float* out_l = dscale_tril;
-  float* out_loc = dloc;
-  if (g.slices > 1) {
-    out_l = static_cast<float*>(workspace);
-    out_loc = out_l + g.slices * D * D;
-  }
+  float* out_l = slice_out(dscale_tril, workspace, g.slices, 0);
+  float* out_loc = slice_out(dloc, workspace, g.slices, g.slices * D * D);
   if (g.mfma) {
-    const dim3 grid((unsigned)g.tiles, (unsigned)ceil_div(g.tiles, mi::kMvnWaves),
+    const dim3 grid((unsigned)g.tiles, (unsigned)ceil_div(g.tiles, mi::kTileWaves),
                     (unsigned)g.slices);
-    hipLaunchKernelGGL(mi::k_mvn_rsample_bwd_mfma, grid, dim3(mi::kMvnThreads), 0, s, dz,
+    hipLaunchKernelGGL(mi::k_mvn_rsample_bwd_mfma, grid, dim3(mi::kTileThreads), 0, s, dz,
                        dz_stride_k, dz_stride_i, K, D, seed, step, step_device, stream_id,
                        particle_offset, eps, (int)g.per, D * D, out_loc, out_l);
   } else {

@@ -112,10 +112,6 @@ __global__ __launch_bounds__(kPeerThreads) void k_peer_allreduce(const mi_peer P
 
 }  // namespace mi
 
-namespace {
-int to_code(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
-}  // namespace
-
 extern "C" {
 
 int mi_peer_region_bytes(int64_t max_floats, size_t* bytes) {

@@ -1107,8 +1107,6 @@ constexpr int kRowElems = 8;
 constexpr int kColUnroll = 4;
 constexpr int64_t kTargetBlocks = 2048;
 
-int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 bool validate_group(const mi_group* g) {
   if (g == nullptr || g->K < 1 || g->N < 1) return false;
   if (g->num_sites < 1 || g->num_sites > MI_MAX_SITES) return false;
@@ -1390,8 +1388,6 @@ size_t workspace_bytes(const mi_group* g, const Plan& p) {
   return finalize_offset(g, p) +
          mi_finalize_scratch_bytes(p.nseg, g->K, g->num_sites + g->num_slots);
 }
-
-int to_code(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 
 }  // namespace
 

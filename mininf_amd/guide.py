@@ -18,6 +18,7 @@ exactly as the oracle's sample-injection protocol does.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import dataclasses
 import os
@@ -83,6 +84,31 @@ def _philox_key(cfg: DrawConfig) -> Tuple[int, int]:
     return cfg.seed & 0xFFFFFFFFFFFFFFFF, cfg.step & 0xFFFFFFFFFFFFFFFF
 
 
+def _workspace(query: str, *dims: int, device: torch.device) -> Tuple[torch.Tensor, int]:
+    """The scratch buffer a sampler's backward asks for through ``query(*dims, &bytes)`` (never
+    empty: the library takes its address) and the size asked for."""
+    size = ctypes.c_size_t()
+    nat.check(getattr(nat.lib(), query)(*dims, ctypes.byref(size)), query)
+    return torch.empty(max(1, size.value), dtype=torch.uint8, device=device), size.value
+
+
+def _float32(grad: torch.Tensor) -> torch.Tensor:
+    """An incoming gradient as the float32 the backward kernels read (any strides)."""
+    return grad if grad.dtype == torch.float32 else grad.to(torch.float32)
+
+
+def _inject(cfg: DrawConfig, device: torch.device, *shape: int) -> None:
+    """Normalise injected noise, if any, to the contiguous float32 [K, *shape] the samplers read."""
+    if cfg.noise is not None:
+        cfg.noise = cfg.noise.to(device=device, dtype=torch.float32).reshape(cfg.K, *shape) \
+            .contiguous()
+
+
+# factors the native "mvn", "dirichlet" and "lowrank" samplers drew in the last draw_all
+# (EvidenceLowerBoundLoss.last_fusions["<family>_draws"])
+_DRAWS: "collections.Counter[str]" = collections.Counter()
+
+
 class _NormalRsampleFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfg: DrawConfig, loc: torch.Tensor, loc_s: int, scale: torch.Tensor,
@@ -108,18 +134,15 @@ class _NormalRsampleFn(torch.autograd.Function):
         (scale,) = ctx.saved_tensors
         N, K = ctx.N, cfg.K
         device = dz.device
-        size = ctypes.c_size_t()
-        lib = nat.lib()
-        nat.check(lib.mi_normal_rsample_backward_workspace_bytes(K, N, ctypes.byref(size)),
-                  "mi_normal_rsample_backward_workspace_bytes")
-        workspace = torch.empty(max(1, size.value), dtype=torch.uint8, device=device)
+        workspace, size = _workspace("mi_normal_rsample_backward_workspace_bytes", K, N,
+                                     device=device)
         dloc = torch.empty(N, dtype=torch.float32, device=device)
         deps_scale = torch.empty(N, dtype=torch.float32, device=device)
         seed, step = _philox_key(cfg)
-        nat.check(lib.mi_normal_rsample_backward(
+        nat.check(nat.lib().mi_normal_rsample_backward(
             dz.data_ptr(), dz.stride(0), dz.stride(1), K, N, seed, step,
             nat.ptr(backward_step(cfg)), cfg.stream_id, cfg.particle_offset, cfg.element_offset,
-            nat.ptr(cfg.noise), workspace.data_ptr(), size.value,
+            nat.ptr(cfg.noise), workspace.data_ptr(), size,
             dloc.data_ptr(), deps_scale.data_ptr(), nat.stream_handle(device)),
             "mi_normal_rsample_backward")
         # dz/dscale = eps: the kernel returns sum_k dz * eps directly.
@@ -318,16 +341,13 @@ class _BetaRsampleFn(torch.autograd.Function):
         x, conc = ctx.saved_tensors
         K, N = ctx.K, ctx.N
         device = dx.device
-        size = ctypes.c_size_t()
-        lib = nat.lib()
-        nat.check(lib.mi_beta_rsample_backward_workspace_bytes(K, N, ctypes.byref(size)),
-                  "mi_beta_rsample_backward_workspace_bytes")
-        workspace = torch.empty(max(1, size.value), dtype=torch.uint8, device=device)
+        workspace, size = _workspace("mi_beta_rsample_backward_workspace_bytes", K, N,
+                                     device=device)
         dconc = torch.empty((N, 2), dtype=torch.float32, device=device)
         base, out = conc.data_ptr(), dconc.data_ptr()
-        nat.check(lib.mi_beta_rsample_backward(
+        nat.check(nat.lib().mi_beta_rsample_backward(
             dx.data_ptr(), dx.stride(0), dx.stride(1), x.data_ptr(), base, 2, base + 4, 2, K, N,
-            workspace.data_ptr(), size.value, out, 2, out + 4, 2, nat.stream_handle(device)),
+            workspace.data_ptr(), size, out, 2, out + 4, 2, nat.stream_handle(device)),
             "mi_beta_rsample_backward")
         return None, dconc
 
@@ -372,16 +392,13 @@ class _GammaRsampleFn(torch.autograd.Function):
         conc_s, rate_s = ctx.strides
         K, N = ctx.K, ctx.N
         device = dx.device
-        lib = nat.lib()
-        size = ctypes.c_size_t()
-        nat.check(lib.mi_gamma_rsample_backward_workspace_bytes(K, N, ctypes.byref(size)),
-                  "mi_gamma_rsample_backward_workspace_bytes")
-        workspace = torch.empty(max(1, size.value), dtype=torch.uint8, device=device)
+        workspace, size = _workspace("mi_gamma_rsample_backward_workspace_bytes", K, N,
+                                     device=device)
         dconc = torch.empty(N, dtype=torch.float32, device=device)
         drate = torch.empty(N, dtype=torch.float32, device=device)
-        nat.check(lib.mi_gamma_rsample_backward(
+        nat.check(nat.lib().mi_gamma_rsample_backward(
             dx.data_ptr(), dx.stride(0), dx.stride(1), g.data_ptr(), conc.data_ptr(), conc_s,
-            rate.data_ptr(), rate_s, K, N, workspace.data_ptr(), size.value, dconc.data_ptr(), 1,
+            rate.data_ptr(), rate_s, K, N, workspace.data_ptr(), size, dconc.data_ptr(), 1,
             drate.data_ptr(), 1, nat.stream_handle(device)), "mi_gamma_rsample_backward")
         # per element; a broadcast parameter's expand backward sums them
         return None, dconc, None, drate, None
@@ -425,32 +442,22 @@ class _MvnRsampleFn(torch.autograd.Function):
     def backward(ctx, dz: torch.Tensor):  # type: ignore[override]
         cfg: DrawConfig = ctx.cfg
         D, K = ctx.D, cfg.K
-        device = dz.device
-        if dz.dtype != torch.float32:
-            dz = dz.to(torch.float32)
-        size = ctypes.c_size_t()
-        lib = nat.lib()
-        nat.check(lib.mi_mvn_rsample_backward_workspace_bytes(K, D, ctypes.byref(size)),
-                  "mi_mvn_rsample_backward_workspace_bytes")
-        workspace = torch.empty(max(1, size.value), dtype=torch.uint8, device=device)
+        device, dz = dz.device, _float32(dz)
+        workspace, size = _workspace("mi_mvn_rsample_backward_workspace_bytes", K, D,
+                                     device=device)
         dloc = torch.empty(D, dtype=torch.float32, device=device)
         dtril = torch.empty((D, D), dtype=torch.float32, device=device)
         seed, step = _philox_key(cfg)
-        nat.check(lib.mi_mvn_rsample_backward(
+        nat.check(nat.lib().mi_mvn_rsample_backward(
             dz.data_ptr(), dz.stride(0), dz.stride(1), K, D, seed, step,
             nat.ptr(backward_step(cfg)), cfg.stream_id, cfg.particle_offset, nat.ptr(cfg.noise),
-            workspace.data_ptr(), size.value, dloc.data_ptr(), dtril.data_ptr(),
+            workspace.data_ptr(), size, dloc.data_ptr(), dtril.data_ptr(),
             nat.stream_handle(device)), "mi_mvn_rsample_backward")
         return None, dloc, dtril
 
 
-# factors the native MultivariateNormal sampler drew in the last draw_all
-# (EvidenceLowerBoundLoss.last_fusions["mvn_draws"])
-_MVN_DRAWS = 0
-
-
 def mvn_draws() -> int:
-    return _MVN_DRAWS
+    return _DRAWS["mvn"]
 
 
 def native_lowrank(distribution) -> bool:
@@ -499,33 +506,23 @@ class _LowRankRsampleFn(torch.autograd.Function):
         cfg: DrawConfig = ctx.cfg
         (cov_diag,) = ctx.saved_tensors
         (D, R), K = ctx.shape, cfg.K
-        device = dz.device
-        if dz.dtype != torch.float32:
-            dz = dz.to(torch.float32)
-        size = ctypes.c_size_t()
-        lib = nat.lib()
-        nat.check(lib.mi_lowrank_rsample_backward_workspace_bytes(K, D, R, ctypes.byref(size)),
-                  "mi_lowrank_rsample_backward_workspace_bytes")
-        workspace = torch.empty(max(1, size.value), dtype=torch.uint8, device=device)
+        device, dz = dz.device, _float32(dz)
+        workspace, size = _workspace("mi_lowrank_rsample_backward_workspace_bytes", K, D, R,
+                                     device=device)
         dloc = torch.empty(D, dtype=torch.float32, device=device)
         dfactor = torch.empty((D, R), dtype=torch.float32, device=device)
         ddiag = torch.empty(D, dtype=torch.float32, device=device)
         seed, step = _philox_key(cfg)
-        nat.check(lib.mi_lowrank_rsample_backward(
+        nat.check(nat.lib().mi_lowrank_rsample_backward(
             dz.data_ptr(), dz.stride(0), dz.stride(1), cov_diag.data_ptr(), K, D, R, seed, step,
             nat.ptr(backward_step(cfg)), cfg.stream_id, cfg.particle_offset, nat.ptr(cfg.noise),
-            workspace.data_ptr(), size.value, dloc.data_ptr(), dfactor.data_ptr(),
+            workspace.data_ptr(), size, dloc.data_ptr(), dfactor.data_ptr(),
             ddiag.data_ptr(), nat.stream_handle(device)), "mi_lowrank_rsample_backward")
         return None, dloc, dfactor, ddiag
 
 
-# factors the native LowRankMultivariateNormal sampler drew in the last draw_all
-# (EvidenceLowerBoundLoss.last_fusions["lowrank_draws"])
-_LOWRANK_DRAWS = 0
-
-
 def lowrank_draws() -> int:
-    return _LOWRANK_DRAWS
+    return _DRAWS["lowrank"]
 
 
 def native_dirichlet(distribution) -> bool:
@@ -572,18 +569,13 @@ class _DirichletRsampleFn(torch.autograd.Function):
     def backward(ctx, dx: torch.Tensor):  # type: ignore[override]
         x, conc = ctx.saved_tensors
         K, N, C = x.shape
-        device = x.device
-        if dx.dtype != torch.float32:
-            dx = dx.to(torch.float32)
-        size = ctypes.c_size_t()
-        lib = nat.lib()
-        nat.check(lib.mi_dirichlet_rsample_backward_workspace_bytes(K, N, C, ctypes.byref(size)),
-                  "mi_dirichlet_rsample_backward_workspace_bytes")
-        workspace = torch.empty(max(1, size.value), dtype=torch.uint8, device=device)
+        device, dx = x.device, _float32(dx)
+        workspace, size = _workspace("mi_dirichlet_rsample_backward_workspace_bytes", K, N, C,
+                                     device=device)
         dconc = torch.empty((N, C), dtype=torch.float32, device=device)
-        nat.check(lib.mi_dirichlet_rsample_backward(
+        nat.check(nat.lib().mi_dirichlet_rsample_backward(
             dx.data_ptr(), dx.stride(0), dx.stride(1), dx.stride(2), x.data_ptr(), conc.data_ptr(),
-            K, N, C, workspace.data_ptr(), size.value, dconc.data_ptr(),
+            K, N, C, workspace.data_ptr(), size, dconc.data_ptr(),
             nat.stream_handle(device)), "mi_dirichlet_rsample_backward")
         return None, dconc
 
@@ -612,13 +604,8 @@ def dirichlet_entropy(distribution: Dirichlet) -> torch.Tensor:
     return _DirichletEntropyFn.apply(_dirichlet_rows(distribution))
 
 
-# factors the native Dirichlet sampler drew in the last draw_all
-# (EvidenceLowerBoundLoss.last_fusions["dirichlet_draws"])
-_DIRICHLET_DRAWS = 0
-
-
 def dirichlet_draws() -> int:
-    return _DIRICHLET_DRAWS
+    return _DRAWS["dirichlet"]
 
 
 # ---- deferred small Normal draws ---------------------------------------------------------------
@@ -878,10 +865,8 @@ def draw(distribution: Distribution, cfg: DrawConfig, lazy: bool = False) -> tor
         nat.require_device(distribution.loc, "guide Normal.loc")
         loc, loc_s = _flat_param(distribution.loc, N)
         scale, scale_s = _flat_param(distribution.scale, N)
-        if cfg.noise is not None:
-            cfg.noise = cfg.noise.to(device=loc.device, dtype=torch.float32).reshape(cfg.K, N) \
-                .contiguous()
-        elif lazy and _fusable_normal(distribution, N):
+        _inject(cfg, loc.device, N)
+        if cfg.noise is None and lazy and _fusable_normal(distribution, N):
             # never read (recognised by its address; other uses re-trace with real draws)
             buffer = torch.empty(1, dtype=torch.float32, device=loc.device)
             placeholder = buffer.expand((cfg.K,) + tuple(shape))
@@ -896,9 +881,7 @@ def draw(distribution: Distribution, cfg: DrawConfig, lazy: bool = False) -> tor
         N = max(1, int(shape.numel()))
         conc = beta_concentration(distribution, N)
         nat.require_device(conc, "guide Beta concentration")
-        if cfg.noise is not None:
-            cfg.noise = cfg.noise.to(device=conc.device, dtype=torch.float32).reshape(cfg.K, N) \
-                .contiguous()
+        _inject(cfg, conc.device, N)
         x = _BetaRsampleFn.apply(cfg, conc)
         _DRAWN[x.data_ptr()] = Drawn(BETA_FAMILY, cfg, x, N, _beta_dgrad(x, conc, cfg.K, N),
                                      conc)
@@ -908,49 +891,38 @@ def draw(distribution: Distribution, cfg: DrawConfig, lazy: bool = False) -> tor
         N = max(1, int(shape.numel()))
         nat.require_device(distribution.concentration, "guide Gamma concentration")
         conc, conc_s, rate, rate_s = gamma_params(distribution, N)
-        if cfg.noise is not None:   # injected standard draws g, [K, *shape]
-            cfg.noise = cfg.noise.to(device=conc.device, dtype=torch.float32).reshape(cfg.K, N) \
-                .contiguous()
+        _inject(cfg, conc.device, N)   # standard draws g, [K, *shape]
         x = _GammaRsampleFn.apply(cfg, conc, conc_s, rate, rate_s)
         return x.reshape((cfg.K,) + tuple(shape))
     if native_mvn(distribution):
         # the public properties: scale_tril carries the autograd of a covariance_matrix /
         # precision_matrix parameterisation
-        global _MVN_DRAWS
         D = int(distribution.event_shape[0])
         loc = distribution.loc.reshape(D).contiguous()
         scale_tril = distribution.scale_tril.reshape(D, D)
         if scale_tril.dtype != torch.float32:
             raise nat.NativeError(f"guide parameters must be float32, got {scale_tril.dtype}")
         scale_tril = scale_tril.contiguous()
-        if cfg.noise is not None:   # injected eps, [K, D]
-            cfg.noise = cfg.noise.to(device=loc.device, dtype=torch.float32).reshape(cfg.K, D) \
-                .contiguous()
-        _MVN_DRAWS += 1
+        _inject(cfg, loc.device, D)   # eps, [K, D]
+        _DRAWS["mvn"] += 1
         return _MvnRsampleFn.apply(cfg, loc, scale_tril)
     if native_dirichlet(distribution):
-        global _DIRICHLET_DRAWS
         conc = _dirichlet_rows(distribution)
         N, C = conc.shape
-        if cfg.noise is not None:   # injected standard draws g, [K, *batch, C]
-            cfg.noise = cfg.noise.to(device=conc.device, dtype=torch.float32) \
-                .reshape(cfg.K, N, C).contiguous()
-        _DIRICHLET_DRAWS += 1
+        _inject(cfg, conc.device, N, C)   # standard draws g, [K, *batch, C]
+        _DRAWS["dirichlet"] += 1
         x = _DirichletRsampleFn.apply(cfg, conc)
         return x.reshape((cfg.K,) + tuple(distribution.batch_shape) + (C,))
     if native_lowrank(distribution):
         # the public loc and the unbroadcast cov_factor / cov_diag (of an unbatched factor: the
         # constructor's own arguments, which carry the autograd of the parameterisation)
-        global _LOWRANK_DRAWS
         cov_factor = distribution._unbroadcasted_cov_factor
         cov_diag = distribution._unbroadcasted_cov_diag
         fill_exp(cov_diag)
         D, R = (int(n) for n in cov_factor.shape)
         loc = distribution.loc.reshape(D).contiguous()
-        if cfg.noise is not None:   # injected eps_D | eps_W, [K, D + R]
-            cfg.noise = cfg.noise.to(device=loc.device, dtype=torch.float32) \
-                .reshape(cfg.K, D + R).contiguous()
-        _LOWRANK_DRAWS += 1
+        _inject(cfg, loc.device, D + R)   # eps_D | eps_W, [K, D + R]
+        _DRAWS["lowrank"] += 1
         return _LowRankRsampleFn.apply(cfg, loc, cov_factor.contiguous(), cov_diag.contiguous())
     if cfg.noise is not None:
         return cfg.noise
@@ -968,10 +940,9 @@ def draw_all(approximation: Dict[str, Distribution], K: int, seed: int, step: in
     Normal factors become :class:`LazyDraw` placeholders evaluated inside the site kernels.
     ``element_offsets``: global index of element 0 of data-sharded factors (multiples of 4).
     """
-    global _MVN_DRAWS, _DIRICHLET_DRAWS, _LOWRANK_DRAWS
     _LAZY.clear()
     _DRAWN.clear()
-    _MVN_DRAWS = _DIRICHLET_DRAWS = _LOWRANK_DRAWS = 0
+    _DRAWS.clear()
     flush_draws(claimed=True)
     samples = {}
     for stream_id, (name, factor) in enumerate(approximation.items()):

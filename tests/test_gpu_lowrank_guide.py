@@ -132,8 +132,12 @@ def test_backward_matches_float64(device, D, R, K):
     transposed = contiguous.t().contiguous().t()          # strides (1, K)
     padded = torch.zeros(K, D + 3, device=device)[:, 1:D + 1]   # row stride D + 3, offset view
     padded.copy_(contiguous)
+    first = None
     for dz in (contiguous, transposed, padded):
         dloc, dW, dd = rsample_backward(device, dz, d, K, D, R)
+        # the kernels read the same values in the same order whatever the strides
+        first = first or (dloc, dW, dd)
+        assert all(torch.equal(got, ref) for got, ref in zip((dloc, dW, dd), first))
         assert (np.abs(host64(dloc) - want_loc) <= bound_loc).all()
         err_W = np.abs(host64(dW) - want_W)
         assert (err_W <= bound_W).all(), (err_W / bound_W).max()

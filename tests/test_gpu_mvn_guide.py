@@ -104,9 +104,7 @@ def test_forward_matches_restatement(device, D, K):
 
 
 # ---- 2. backward against float64 ---------------------------------------------------------------
-@pytest.mark.parametrize("D", DS)
-@pytest.mark.parametrize("K", KS)
-def test_backward_matches_float64(device, D, K):
+def check_backward(device, D, K):
     rng = np.random.default_rng(7 + 100 * D + K)
     eps = oracle_eps(K, D)
     dz64 = f32(rng.standard_normal((K, D)))
@@ -119,8 +117,12 @@ def test_backward_matches_float64(device, D, K):
     transposed = contiguous.t().contiguous().t()          # strides (1, K)
     padded = torch.zeros(K, D + 3, device=device)[:, 1:D + 1]   # row stride D + 3, offset view
     padded.copy_(contiguous)
+    first = None
     for dz in (contiguous, transposed, padded):
         dloc, dtril = rsample_backward(device, dz, K, D)
+        # the kernels read the same values in the same order whatever the strides
+        first = first or (dloc, dtril)
+        assert torch.equal(dloc, first[0]) and torch.equal(dtril, first[1])
         got_loc = dloc.cpu().numpy().astype(np.float64)
         got_tril = dtril.cpu().numpy().astype(np.float64)
         assert (np.abs(got_loc - want_loc) <= bound_loc + 1e-30).all()
@@ -128,6 +130,18 @@ def test_backward_matches_float64(device, D, K):
         assert (np.tril(err) <= bound_tril).all(), (np.tril(err) / bound_tril).max()
         upper = dtril.cpu().numpy()[np.triu_indices(D, 1)]
         assert (upper == 0.0).all() and not np.signbit(upper).any()
+
+
+@pytest.mark.parametrize("D", DS)
+@pytest.mark.parametrize("K", KS)
+def test_backward_matches_float64(device, D, K):
+    check_backward(device, D, K)
+
+
+def test_backward_sums_valu_slices(device):
+    """D < 32 with K > 128: the VALU backward runs max(64, ceil(K / 256)) particles per slice, so
+    K = 130 is three slices (the last one partial) summed by the slice combination."""
+    check_backward(device, 3, 130)
 
 
 @pytest.mark.parametrize("D", (3, 33))
