@@ -127,17 +127,27 @@ def _grad_small_beta(x, a, b):
     return 0.0 if math.isnan(r) else r
 
 
-def _grad_mid(x, a, b):
+def _mid_in_band(x, a, b):
+    """Whether x lies within 0.1 sd of the mean of Beta(a, b): the polynomial band of _grad_mid."""
     t = a + b
     mean = a / t
     sd = math.sqrt(a * b / (t + 1)) / t
-    if mean - 0.1 * sd <= x <= mean + 0.1 * sd:
-        poly = (47 * x * b ** 4 + a * ((43 + 20 * (16 + 27 * b) * x) * b ** 3 + a * (
-            3 * (59 + 180 * b - 90 * x) * b * b + a * ((453 + 1620 * b * (1 - x) - 455 * x) * b
-                                                       + a * (8 * (1 - x) * (135 * b - 11))))))
-        pre_num = (1 + 12 * a) * (1 + 12 * b) / (t * t)
-        pre_den = 12960 * a ** 3 * b * b * (1 + 12 * t)
-        return pre_num / (1 - x) * poly / pre_den
+    return mean - 0.1 * sd <= x <= mean + 0.1 * sd
+
+
+def _grad_mid_poly(x, a, b):
+    t = a + b
+    poly = (47 * x * b ** 4 + a * ((43 + 20 * (16 + 27 * b) * x) * b ** 3 + a * (
+        3 * (59 + 180 * b - 90 * x) * b * b + a * ((453 + 1620 * b * (1 - x) - 455 * x) * b
+                                                   + a * (8 * (1 - x) * (135 * b - 11))))))
+    pre_num = (1 + 12 * a) * (1 + 12 * b) / (t * t)
+    pre_den = 12960 * a ** 3 * b * b * (1 + 12 * t)
+    return pre_num / (1 - x) * poly / pre_den
+
+
+def _grad_mid_rice(x, a, b):
+    t = a + b
+    mean = a / t
     prefactor = -x / math.sqrt(2 * a * b / t)
     stirling = ((1 + 1 / (12 * a) + 1 / (288 * a * a)) * (1 + 1 / (12 * b) + 1 / (288 * b * b))
                 / (1 + 1 / (12 * t) + 1 / (288 * t * t)))
@@ -148,6 +158,10 @@ def _grad_mid(x, a, b):
     term3 = math.sqrt(8 * a * b / t) / (b * x + a * (x - 1))
     term4 = (b * math.log(b / (t * (1 - x))) + a * math.log(a / (t * x))) ** -1.5
     return stirling * prefactor * (term1 + term2 * (term3 + (term4 if x < mean else -term4)))
+
+
+def _grad_mid(x, a, b):
+    return _grad_mid_poly(x, a, b) if _mid_in_band(x, a, b) else _grad_mid_rice(x, a, b)
 
 
 # Coefficient table of the rational correction, as published in torch's Distributions.h.
@@ -185,6 +199,11 @@ def dirichlet_grad_one(x, alpha, total):
         return -_grad_small_beta(1 - x, beta_, alpha)
     if alpha > 6 and beta_ > 6:
         return _grad_mid(x, alpha, beta_)
+    return _grad_rational(x, alpha, total)
+
+
+def _grad_rational(x, alpha, total):
+    beta_ = total - alpha
     u = math.log(x)
     a = math.log(alpha) - u
     b = math.log(total) - a
@@ -287,7 +306,10 @@ def standard_gamma_grad(alpha, x):
             pdf = xv ** (a - 1.0) * math.exp(-xv)
             cdf = pxa * s1
             cdf_a = (math.log(xv) - float(special.digamma(a))) * cdf - pxa * s2
-            res = -cdf_a / pdf
+            if pdf == 0.0:   # x^alpha underflows: IEEE division (0 / 0 is NaN), not Python's error
+                res = math.nan if cdf_a == 0.0 else math.copysign(math.inf, -cdf_a)
+            else:
+                res = -cdf_a / pdf
             out[idx] = 0.0 if math.isnan(res) else res
         elif a > 8.0:
             if float(f(0.9)) * a <= xv <= float(f(1.1)) * a:

@@ -14,6 +14,7 @@ import mininf_amd as mi
 from mininf_amd import _native as nat, engine, guide
 from mininf_amd.particles import SiteRecord
 from oracle import build as oracle_build, elbo as oracle, logprob as lpf
+from tests import implicit_grad_cases as grad_cases
 from tests.conftest import golden
 
 pytestmark = pytest.mark.gpu
@@ -514,18 +515,40 @@ def test_fused_guide_draw_matches_materialised(device, n, use_exp, monkeypatch):
         torch.testing.assert_close(fused[1][name], plain[1][name], rtol=1e-5, atol=1e-5)
 
 
-def _absorb_cases(device, case):
+# Guide pairs beyond the small-alpha and rational regimes of dirichlet_grad, with the regimes
+# their injected draws (the designed grid's points for the pair) must reach.
+REGIME_PAIRS = {(0.05, 0.05): {"small_alpha", "small_beta"},
+                (8.0, 12.0): {"small_alpha", "small_beta", "mid_rice", "mid_poly"},
+                (40.0, 6.1): {"small_alpha", "small_beta", "mid_rice", "mid_poly"},
+                (300.0, 700.0): {"small_alpha", "small_beta", "mid_rice", "mid_poly"}}
+
+
+def _regime_draws(pair, K, device):
+    """[K, 1] draws cycling through the grid's points for `pair` (without the two extremes, 1e-30
+    and 1 - 2^-24, where the model's own float32 densities lose their meaning), and a check that
+    they reach the pair's regimes."""
+    column = grad_cases.beta_column(*pair)
+    column = column[(column >= np.float32(1e-6)) & (column < grad_cases.X_TOP)]
+    c1, c0 = np.float32(pair[0]), np.float32(pair[1])
+    reached = set(grad_cases.regime(column, c1, np.float32(c1 + c0)).tolist())
+    assert REGIME_PAIRS[pair] <= reached, (pair, reached)
+    draws = column[np.arange(K) % len(column)].reshape(K, 1)
+    return torch.as_tensor(draws, device=device).contiguous()
+
+
+def _absorb_cases(device, case, pair=(1.7, 2.6), n=5000, K=2048):
     """Models whose guide draws the ELBO backward can absorb (or must not)."""
     rng = np.random.default_rng(12)
     if case == "beta_scalar":   # C2-shaped: one Beta factor, many particles (cross-slice sums)
-        x = torch.as_tensor((rng.random(5000) < 0.7).astype(np.float32), device=device)
+        x = torch.as_tensor((rng.random(n) < 0.7).astype(np.float32), device=device)
 
         def model():
             theta = mi.sample("theta", Beta(2.0, 2.0))
-            mi.sample("x", Bernoulli(theta), sample_shape=[5000])
+            mi.sample("x", Bernoulli(theta), sample_shape=[n])
         approx = mi.nn.ParameterizedFactorizedDistribution(
-            theta=mi.nn.ParameterizedDistribution(Beta, concentration1=1.7, concentration0=2.6))
-        return mi.condition(model, x=x), approx.to(device), 2048
+            theta=mi.nn.ParameterizedDistribution(Beta, concentration1=pair[0],
+                                                  concentration0=pair[1]))
+        return mi.condition(model, x=x), approx.to(device), K
     if case == "two_factor":
         cond, approx, _, K = _two_factor_case(device, n=700, K=16)
         return cond, approx, K
@@ -553,7 +576,10 @@ def _absorb_cases(device, case):
 
 @pytest.mark.parametrize("case", ["beta_scalar", "beta_scalar_inline", "beta_scalar_dgrad",
                                   "two_factor", "linear",
-                                  "linear_sigma", "hierarchical", "exp_use"])
+                                  "linear_sigma", "hierarchical", "exp_use"] +
+                         [f"{variant}@{c1:g},{c0:g}" for c1, c0 in REGIME_PAIRS
+                          for variant in ("beta_scalar", "beta_scalar_inline",
+                                          "beta_scalar_dgrad")])
 def test_absorbed_draws_match_autograd(device, case, monkeypatch):
     """
     Guide draws whose backward the ELBO kernel absorbs (mi_factor draw_kind: Beta implicit
@@ -562,19 +588,30 @@ def test_absorbed_draws_match_autograd(device, case, monkeypatch):
     Beta: the implicit-gradient factors computed by extra workgroups of the site launch (mi_side,
     the default), inside mi_elbo_forward (beta_scalar_inline, MININF_AMD_BETA_SIDE=0), or by
     mi_beta_dgrad on a side stream (beta_scalar_dgrad, MININF_AMD_BETA_DGRAD=1).
+    `case@c1,c0`: the Beta case with that guide pair, K = 96, N = 300 and injected draws that reach
+    the pair's regimes of dirichlet_grad (REGIME_PAIRS), the mid regimes and the band among them;
+    N = 1030 for the side-job variant, which needs the BCAST kernel (N >= 1024).
     """
+    case, _, pair = case.partition("@")
+    pair = tuple(float(v) for v in pair.split(",")) if pair else None
+    n = 1030 if case == "beta_scalar" else 300   # (with a pair)
     if case == "beta_scalar_dgrad":
         monkeypatch.setenv("MININF_AMD_BETA_DGRAD", "1")
         case = "beta_scalar"
     if case == "beta_scalar_inline":
         monkeypatch.setenv("MININF_AMD_BETA_SIDE", "0")
         case = "beta_scalar"
-    cond, approx, K = _absorb_cases(device, case)
+    noise = None
+    if pair is None:
+        cond, approx, K = _absorb_cases(device, case)
+    else:
+        cond, approx, K = _absorb_cases(device, case, pair=pair, n=n, K=96)
+        noise = {"theta": _regime_draws(pair, K, device).reshape(K)}
 
     def run(scale=1.0):
         for q in approx.parameters():
             q.grad = None
-        loss = mi.nn.EvidenceLowerBoundLoss(num_particles=K, seed=3)(cond, approx())
+        loss = mi.nn.EvidenceLowerBoundLoss(num_particles=K, seed=3)(cond, approx(), _noise=noise)
         (scale * loss).backward()
         return float(loss), {k: q.grad.detach().clone() for k, q in approx.named_parameters()}
 
@@ -640,17 +677,27 @@ def test_fused_beta_guide_matches_torch_construction(device):
         bad()
 
 
-@pytest.mark.parametrize("N,K", [(5000, 2048), (3000, 96)])
-def test_bcast_side_job_matches_beta_dgrad(device, N, K):
+@pytest.mark.parametrize("N,K,pair", [pytest.param(5000, 2048, None, id="5000-2048"),
+                                      pytest.param(3000, 96, None, id="3000-96")] +
+                         [pytest.param(1030, 96, pair, id=f"1030-96-{pair[0]:g}-{pair[1]:g}")
+                          for pair in REGIME_PAIRS])
+def test_bcast_side_job_matches_beta_dgrad(device, N, K, pair):
     """
     The Beta implicit-gradient factors carried as extra workgroups of the BCAST site launch
     (mi_side) are bit-identical to mi_beta_dgrad's, and the site results are unchanged by them.
+    With a `pair`: that guide pair and draws from the designed grid that reach its regimes of
+    dirichlet_grad (REGIME_PAIRS), at N = 1030: the BCAST kernel, and so the side job, exists from
+    N = 1024 (bcast_eligible).
     """
     rng = np.random.default_rng(N)
     x = (rng.random(N) < 0.6).astype(np.float32)
-    conc = torch.as_tensor([[1.7, 2.6]], dtype=torch.float32, device=device)
-    draws = torch.distributions.Beta(torch.tensor(1.7), torch.tensor(2.6)).sample((K, 1))
-    draws = draws.to(device).contiguous()
+    if pair is None:
+        conc = torch.as_tensor([[1.7, 2.6]], dtype=torch.float32, device=device)
+        draws = torch.distributions.Beta(torch.tensor(1.7), torch.tensor(2.6)).sample((K, 1))
+        draws = draws.to(device).contiguous()
+    else:
+        conc = torch.as_tensor([pair], dtype=torch.float32, device=device)
+        draws = _regime_draws(pair, K, device)
     probs = draws.reshape(K, 1).clone().requires_grad_()
     base = launch("bernoulli_probs", [probs], torch.as_tensor(x, device=device), device, K=K, N=N)
 
