@@ -628,6 +628,71 @@ int mi_philox_normal(int64_t K, int64_t N, uint64_t seed, uint64_t step, uint32_
 int mi_philox4x32(const uint32_t* ctr, int64_t count, uint32_t key0, uint32_t key1, uint32_t* out,
                   void* stream);
 
+/* ---- posterior-predictive draws (broadcast_samples, reference core.py:548-584) ---------------- */
+
+/* Draws of the sites a predictive run simulates (SampleTracer.sample, core.py:192-204), on the
+ * guide generator. The logical space is [S, M]: S samples of M elements, flat element
+ * e = s * M + j, which is mi_normal_rsample's layout with K = 1 and N = S * M. A parameter is a
+ * device pointer and two element strides (stride_s, stride_j), either of which may be 0, so a
+ * per-sample scalar, a per-element constant and a dense parameter are read in place. A value is a
+ * function of (seed, stream_id, s, j, M): not of S, so the first S' samples of a run are the run
+ * with S = S'. All three are asynchronous on `stream`, allocate nothing, index in int64 and check
+ * their arguments before any device work. */
+
+/* Fixed-consumption families. Element e takes word e % 4 of the Philox block of quad e / 4 at step
+ * 0, sub-stream 0, particle 0 (mi_normal_rsample's counter): u = ((word >> 8) + 0.5) * 2^-24, or,
+ * for the two normal-based families, the standard normal eps mi_philox_normal reports for e.
+ *   MI_PRED_BERNOULLI_PROBS   a = probs           u < a ? 1 : 0
+ *   MI_PRED_BERNOULLI_LOGITS  a = logits          u < 1 / (1 + expf(-a)) ? 1 : 0
+ *   MI_PRED_EXPONENTIAL       a = rate            -logf(u) / a
+ *   MI_PRED_LAPLACE           a = loc, b = scale  a - b * sign(u - 1/2) * log1pf(-2 |u - 1/2|)
+ *   MI_PRED_CAUCHY            a = loc, b = scale  a + b * tan(pi (u - 1/2))
+ *   MI_PRED_HALF_CAUCHY       a = scale           a * tan(pi u / 2)
+ *   MI_PRED_HALF_NORMAL       a = scale           a * |eps|
+ *   MI_PRED_LOG_NORMAL        a = loc, b = scale  expf(a + eps * b)
+ * u lies on the 24-bit grid (k + 1/2) 2^-24 rounded to float32, so every tail stops at the 2^-25
+ * quantile: an Exponential draw is at most 17.33 / rate, a Cauchy draw at least
+ * loc - scale * 2^25 / pi, |eps| at most 5.89. Above 1/2 the float32 spacing is 2^-24 and the top
+ * grid point rounds to 1.0f; Laplace, Cauchy and HalfCauchy, for which u = 1 is a pole, read it as
+ * 1 - 2^-24, so their upper tail stops at the 2^-24 quantile (Cauchy: loc + scale * 2^24 / pi).
+ * b is read only by the two-parameter families (NULL otherwise). out is float32 [S * M].
+ * S * M <= 2^34 (the quad counter has 32 bits): larger is MI_EUNSUPPORTED. */
+#define MI_PRED_BERNOULLI_PROBS 0
+#define MI_PRED_BERNOULLI_LOGITS 1
+#define MI_PRED_EXPONENTIAL 2
+#define MI_PRED_LAPLACE 3
+#define MI_PRED_CAUCHY 4
+#define MI_PRED_HALF_CAUCHY 5
+#define MI_PRED_HALF_NORMAL 6
+#define MI_PRED_LOG_NORMAL 7
+#define MI_PRED_FAMILIES 8
+int mi_predictive_sample(int family, const float* a, int64_t a_stride_s, int64_t a_stride_j,
+                         const float* b, int64_t b_stride_s, int64_t b_stride_j, int64_t S,
+                         int64_t M, uint64_t seed, uint32_t stream_id, float* out, void* stream);
+
+/* Categorical(logits[S, B, C]) with T replications per sample (the site's sample_shape): row
+ * r = (s * T + t) * B + b reads logits[s * stride_s + b * stride_b + c * stride_c] (stride_s or
+ * stride_b may be 0) and takes word r % 4 of the block of quad r / 4 (the counter above, over rows).
+ *   out[r] = the smallest c with cum_c > u * cum_{C-1},  cum_c = sum_{j <= c} expf(l_j - max_j l_j)
+ * accumulated ascending in fp32 (rows of more than 32 categories: per-lane runs of consecutive
+ * categories joined by a wave prefix sum, which moves cum_c by rounding only). If rounding lets the
+ * search run off the end, out[r] is the last category with a finite logit. out is int64 [S*T*B].
+ * 1 <= C <= MI_PRED_CATEGORICAL_MAX_C and S * T * B <= 2^34: larger is MI_EUNSUPPORTED. */
+#define MI_PRED_CATEGORICAL_MAX_C 1024
+int mi_predictive_categorical(const float* logits, int64_t stride_s, int64_t stride_b,
+                              int64_t stride_c, int64_t S, int64_t T, int64_t B, int64_t C,
+                              uint64_t seed, uint32_t stream_id, int64_t* out, void* stream);
+
+/* Poisson(rate) consumes a variable number of words, so element e reads its own stream of Philox
+ * blocks, mi_gamma_rsample's scheme on the free sub-stream 3:
+ *   counter {e, 0, 0, (stream_id << 8) | (3 << 6) | block}, four words per block.
+ * rate < 10: uniforms are multiplied until the product falls below expf(-rate) (fp32; at most 250
+ * factors). rate >= 10: Hoermann's transformed rejection PTRS (1993) in fp64, two uniforms per
+ * attempt, at most 64 attempts. rate = 0 gives 0; a negative or non-finite rate writes NaN. out
+ * is float32 [S * M]. S * M <= 2^32 (the element counter has 32 bits): larger is MI_EUNSUPPORTED. */
+int mi_predictive_poisson(const float* rate, int64_t stride_s, int64_t stride_j, int64_t S,
+                          int64_t M, uint64_t seed, uint32_t stream_id, float* out, void* stream);
+
 /* ---- linear-predictor sites (Normal(X @ theta, sigma), Bernoulli(logits = X @ theta)) --------- */
 
 /* A site whose location / logits is the model's own product X @ theta of an observed design matrix

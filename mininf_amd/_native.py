@@ -32,6 +32,10 @@ MVN_MAX_N = 1024   # MI_MVN_MAX_N
 DIRICHLET_MAX_C = 1024   # MI_DIRICHLET_MAX_C
 LOWRANK_MAX_R = 128   # MI_LOWRANK_MAX_R
 LOWRANK_MAX_D = 1 << 24   # MI_LOWRANK_MAX_D
+PRED_CATEGORICAL_MAX_C = 1024   # MI_PRED_CATEGORICAL_MAX_C
+# MI_PRED_* family codes of mi_predictive_sample
+(PRED_BERNOULLI_PROBS, PRED_BERNOULLI_LOGITS, PRED_EXPONENTIAL, PRED_LAPLACE, PRED_CAUCHY,
+ PRED_HALF_CAUCHY, PRED_HALF_NORMAL, PRED_LOG_NORMAL) = range(8)
 
 NORMAL, BERNOULLI_LOGITS, BERNOULLI_PROBS, BETA, GAMMA, POISSON, INVERSE_GAMMA = 0, 1, 2, 3, 4, 5, 6
 EXPONENTIAL, LAPLACE, CAUCHY, HALF_NORMAL, HALF_CAUCHY, LOG_NORMAL = 7, 8, 9, 10, 11, 12
@@ -326,6 +330,14 @@ _SIGNATURES = {
     "mi_philox_normal": (ctypes.c_int, [c_i64, c_i64, ctypes.c_uint64, ctypes.c_uint64,
                                         ctypes.c_uint32, c_i64, c_vp, c_vp]),
     "mi_philox4x32": (ctypes.c_int, [c_vp, c_i64, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp]),
+    "mi_predictive_sample": (ctypes.c_int, [ctypes.c_int, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64,
+                                            c_i64, c_i64, ctypes.c_uint64, ctypes.c_uint32, c_vp,
+                                            c_vp]),
+    "mi_predictive_categorical": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,
+                                                 c_i64, ctypes.c_uint64, ctypes.c_uint32, c_vp,
+                                                 c_vp]),
+    "mi_predictive_poisson": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, ctypes.c_uint64,
+                                             ctypes.c_uint32, c_vp, c_vp]),
     "mi_elbo_struct_sizes": (ctypes.c_int, [ctypes.POINTER(ctypes.c_size_t)] * 2),
     "mi_linear_struct_size": (ctypes.c_int, [ctypes.POINTER(ctypes.c_size_t)]),
     "mi_linear_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(Linear),

@@ -856,11 +856,13 @@ def broadcast_particles(model: Callable, states: Dict[str, torch.Tensor]) -> Sta
             tracer.index = None
         return tracer, keys, outputs
 
+    drawn = predictive.native_draws()
     try:
         tracer, keys, outputs = run(False)
     except RuntimeError as error:
         if not _needs_compat(error):
             raise
+        predictive.reset_counts(drawn)   # the abandoned trace's sites are drawn again
         tracer, keys, outputs = run(True)
     values = outputs[:len(keys)]
     failed = [check for check in tracer.checks
