@@ -693,6 +693,63 @@ int mi_predictive_categorical(const float* logits, int64_t stride_s, int64_t str
 int mi_predictive_poisson(const float* rate, int64_t stride_s, int64_t stride_j, int64_t S,
                           int64_t M, uint64_t seed, uint32_t stream_id, float* out, void* stream);
 
+/* ---- guide factors of the one-noise-word families --------------------------------------------- */
+
+/* Exponential, Laplace, Cauchy, HalfCauchy, HalfNormal and LogNormal as guide factors: the draw of
+ * mi_predictive_sample's table above over K particles, its backward and the entropy. `family` is
+ * MI_PRED_EXPONENTIAL .. MI_PRED_LOG_NORMAL (the two Bernoulli codes are MI_EINVAL); a and b are
+ * that table's parameters, each read at i * stride (stride 0: one value for all elements); b is
+ * read only by the two-parameter families (NULL otherwise). All are asynchronous on `stream`,
+ * allocate nothing, index in int64 and check their arguments before any device work.
+ *
+ *   z[k, i] = draw(a[i * a_stride], b[i * b_stride], v[k, i])            (row-major [K, N])
+ * v[k, i] comes from word i % 4 of the Philox block of counter
+ *   {quad i / 4, particle_offset + k, step (+ *step_device), stream_id << 8}
+ * which is mi_normal_rsample's counter: u = ((word >> 8) + 0.5) * 2^-24 for the four uniform
+ * families, the eps mi_philox_normal reports for HalfNormal and LogNormal. Row k at
+ * particle_offset o is row k + o at offset 0. One difference from the predictive draw: here the
+ * Exponential too reads u = 1.0f (the top grid point) as 1 - 2^-24, so no draw is 0 and every draw
+ * lies inside its family's support. A non-NULL `noise` (row-major [K, N]) is read for v instead
+ * (parity mode: neither seed nor step is read). N <= 2^34 and K * ceil(N / 4) <= 2^39: larger is
+ * MI_EUNSUPPORTED. */
+int mi_elementwise_rsample(int family, const float* a, int64_t a_stride, const float* b,
+                           int64_t b_stride, int64_t K, int64_t N, uint64_t seed, uint64_t step,
+                           const uint64_t* step_device, uint32_t stream_id,
+                           int64_t particle_offset, const float* noise, float* z, void* stream);
+
+/* Backward of the draw, reduced over particles; v is regenerated from the counter (or read from
+ * `noise`), z is not needed:
+ *   da[i] = sum_k dz[k * dz_stride_k + i * dz_stride_i] * d z / d a,   db[i] likewise
+ * each written (contiguous [N]) only when its pointer is non-NULL; at least one must be. db is
+ * ignored for the one-parameter families. With t the standardised draw (loc 0, scale 1):
+ *   LogNormal   d/dloc = z, d/dscale = z * eps      Laplace, Cauchy  d/dloc = 1, d/dscale = t
+ *   HalfCauchy, HalfNormal  d/dscale = t            Exponential      d/drate = logf(u) / rate^2
+ * Products and sums are fp64, in an order fixed by (K, N): particle slices write fp32 partials to
+ * the workspace and a second launch adds them in slice order; one slice writes the outputs
+ * directly. */
+int mi_elementwise_rsample_backward_workspace_bytes(int64_t K, int64_t N, size_t* bytes);
+int mi_elementwise_rsample_backward(int family, const float* dz, int64_t dz_stride_k,
+                                    int64_t dz_stride_i, const float* a, int64_t a_stride,
+                                    const float* b, int64_t b_stride, int64_t K, int64_t N,
+                                    uint64_t seed, uint64_t step, const uint64_t* step_device,
+                                    uint32_t stream_id, int64_t particle_offset,
+                                    const float* noise, void* workspace, size_t workspace_bytes,
+                                    float* da, float* db, void* stream);
+
+/* Entropy of the factor summed over its N elements, and its gradient, in one launch: H[0] is the
+ * fp64 sum (fixed order) of the elements' fp32 entropies, written as one float32; da[i] and db[i]
+ * (float32, contiguous [N]) are written only when non-NULL. Per element, torch's entropy() of each
+ * class:
+ *   LogNormal    1/2 + 1/2 log(2 pi) + log(scale) + loc    dloc = 1, dscale = 1 / scale
+ *   Laplace      1 + log(2 scale)                          dloc = 0, dscale = 1 / scale
+ *   Cauchy       log(4 pi scale)                           dloc = 0, dscale = 1 / scale
+ *   HalfCauchy   log(2 pi scale)                           dscale = 1 / scale
+ *   HalfNormal   1/2 + 1/2 log(pi / 2) + log(scale)        dscale = 1 / scale
+ *   Exponential  1 - log(rate)                             drate = -1 / rate */
+int mi_elementwise_entropy(int family, const float* a, int64_t a_stride, const float* b,
+                           int64_t b_stride, int64_t N, float* H, float* da, float* db,
+                           void* stream);
+
 /* ---- linear-predictor sites (Normal(X @ theta, sigma), Bernoulli(logits = X @ theta)) --------- */
 
 /* A site whose location / logits is the model's own product X @ theta of an observed design matrix

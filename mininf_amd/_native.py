@@ -338,6 +338,18 @@ _SIGNATURES = {
                                                  c_vp]),
     "mi_predictive_poisson": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, ctypes.c_uint64,
                                              ctypes.c_uint32, c_vp, c_vp]),
+    "mi_elementwise_rsample": (ctypes.c_int, [ctypes.c_int, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64,
+                                              ctypes.c_uint64, ctypes.c_uint64, c_vp,
+                                              ctypes.c_uint32, c_i64, c_vp, c_vp, c_vp]),
+    "mi_elementwise_rsample_backward_workspace_bytes": (ctypes.c_int, [
+        c_i64, c_i64, ctypes.POINTER(ctypes.c_size_t)]),
+    "mi_elementwise_rsample_backward": (ctypes.c_int, [ctypes.c_int, c_vp, c_i64, c_i64, c_vp,
+                                                       c_i64, c_vp, c_i64, c_i64, c_i64,
+                                                       ctypes.c_uint64, ctypes.c_uint64, c_vp,
+                                                       ctypes.c_uint32, c_i64, c_vp, c_vp,
+                                                       ctypes.c_size_t, c_vp, c_vp, c_vp]),
+    "mi_elementwise_entropy": (ctypes.c_int, [ctypes.c_int, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp,
+                                              c_vp, c_vp, c_vp]),
     "mi_elbo_struct_sizes": (ctypes.c_int, [ctypes.POINTER(ctypes.c_size_t)] * 2),
     "mi_linear_struct_size": (ctypes.c_int, [ctypes.POINTER(ctypes.c_size_t)]),
     "mi_linear_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(Linear),

@@ -10,6 +10,7 @@
 // and two element strides (stride_s, stride_j), either of which may be 0: a per-sample scalar, a
 // per-element constant and a dense parameter are read where they lie. A value is a function of
 // (seed, stream_id, s, j, M) and not of S, the grid or the strides.
+#include "elementwise_draw.hpp"
 #include "gamma_sample.hpp"
 #include "internal.hpp"
 
@@ -26,37 +27,6 @@ struct PredParam {
   const float* p;
   int64_t ss, sj;
 };
-
-// One draw from its noise word: `v` is the element's uniform (u01) or, for the two normal-based
-// families, its standard normal.
-template <int FAMILY>
-MI_DEV float pred_draw(float a, float b, float v) {
-  if (FAMILY == MI_PRED_BERNOULLI_PROBS) return v < a ? 1.0f : 0.0f;
-  if (FAMILY == MI_PRED_BERNOULLI_LOGITS) return v < 1.0f / (1.0f + expf(-a)) ? 1.0f : 0.0f;
-  if (FAMILY == MI_PRED_EXPONENTIAL) return -logf(v) / a;
-  // The top grid point (2^24 - 1/2) 2^-24 rounds to 1.0f, the pole of the three draws below:
-  // they read it as the largest float below 1, so their upper tail stops at the 2^-24 quantile.
-  if (FAMILY == MI_PRED_LAPLACE || FAMILY == MI_PRED_CAUCHY || FAMILY == MI_PRED_HALF_CAUCHY)
-    v = fminf(v, 0.99999994f);
-  if (FAMILY == MI_PRED_LAPLACE) {
-    const float d = v - 0.5f;   // exact: v is on the 24-bit grid
-    return a - b * copysignf(1.0f, d) * log1pf(-2.0f * fabsf(d));
-  }
-  if (FAMILY == MI_PRED_CAUCHY) {
-    // tan(pi (u - 1/2)) from sin and cos of the exact half-turn fraction: no rounding of the
-    // argument, so the result stays accurate up to the last grid point before the pole
-    float s, c;
-    sincospif(v - 0.5f, &s, &c);
-    return fmaf(b, s / c, a);
-  }
-  if (FAMILY == MI_PRED_HALF_CAUCHY) {
-    float s, c;
-    sincospif(0.5f * v, &s, &c);
-    return a * (s / c);
-  }
-  if (FAMILY == MI_PRED_HALF_NORMAL) return a * fabsf(v);
-  return expf(fmaf(v, b, a));   // MI_PRED_LOG_NORMAL
-}
 
 template <int FAMILY>
 __global__ __launch_bounds__(kPredThreads) void k_predictive_sample(

@@ -1921,7 +1921,9 @@ class _ElboPlan:
         mvn_draws: MultivariateNormal guide factors drawn by the native sampler (mi_mvn_rsample);
         dirichlet_draws: Dirichlet guide factors drawn by the native sampler (mi_dirichlet_rsample);
         lowrank_draws: LowRankMultivariateNormal guide factors drawn by the native sampler
-        (mi_lowrank_rsample).
+        (mi_lowrank_rsample); elementwise_draws: Exponential, Laplace, Cauchy, HalfCauchy,
+        HalfNormal and LogNormal guide factors drawn by the native sampler
+        (mi_elementwise_rsample).
         """
         return {
             "folded_priors": sum(l.prior is not None for l in self.launchers) +
@@ -1937,6 +1939,7 @@ class _ElboPlan:
             "mvn_draws": guide.mvn_draws(),
             "dirichlet_draws": guide.dirichlet_draws(),
             "lowrank_draws": guide.lowrank_draws(),
+            "elementwise_draws": guide.elementwise_draws(),
         }
 
     def _reduce_ok(self, assume=None) -> bool:
@@ -2320,7 +2323,8 @@ def entropy_factors(approximation) -> Tuple[List[EntropyFactor], list]:
     """
     Split a factorised guide into factors whose entropy the ELBO kernels evaluate (Normal, Beta,
     Gamma) and the rest (whose entropy torch.distributions evaluates, or -- a native Dirichlet
-    factor, guide.native_dirichlet -- mi_dirichlet_entropy, called by the loss). A
+    factor, guide.native_dirichlet -- mi_dirichlet_entropy, or -- a native one-noise-word factor,
+    guide.native_elementwise -- mi_elementwise_entropy, both called by the loss). A
     LowRankMultivariateNormal factor stays in the rest also when its draws are native
     (guide.native_lowrank): its entropy is torch's, and with it the loss is no longer the fused
     node alone, so its gradients take autograd, never the direct-to-leaf paths.

@@ -2,19 +2,23 @@
 Reparameterised guide sampling over K particles (replaces ``FactorizedDistribution.rsample``,
 reference ``mininf/nn.py:133-145``, with ONE draw per call at ``nn.py:217``).
 
-Normal, Beta, Gamma, Dirichlet, full-covariance MultivariateNormal and LowRankMultivariateNormal
+Normal, Beta, Gamma, Dirichlet, full-covariance MultivariateNormal, LowRankMultivariateNormal,
+Exponential, Laplace, Cauchy, HalfCauchy, HalfNormal and LogNormal
 factors are drawn by HIP kernels from a counter-based Philox generator keyed by (seed, step, factor index, global particle
 index, element), so that K particles split over W GPUs draw exactly the union of what one GPU would
 draw. Other families (and a batched, float64, host-resident or D > MI_MVN_MAX_N
 MultivariateNormal; a subclassed, float64, host-resident or C > MI_DIRICHLET_MAX_C Dirichlet; a
-batched, subclassed, float64, host-resident or R > MI_LOWRANK_MAX_R LowRankMultivariateNormal) use
+batched, subclassed, float64, host-resident or R > MI_LOWRANK_MAX_R LowRankMultivariateNormal; a
+subclassed, float64 or host-resident factor of the last six) use
 their own ``torch.distributions`` ``rsample`` on the device.
 
 Parity mode: ``noise[name]`` injects host-drawn standard normals (Normal factors, [K, *shape];
 MultivariateNormal factors, [K, D]; LowRankMultivariateNormal factors, [K, D + R]: eps_D, then
 eps_W), the draws themselves (Beta factors) or the standard Gamma
 draws g with x = g / rate (Gamma factors) or x = g / sum(g) (Dirichlet factors, [K, *batch, C]),
-exactly as the oracle's sample-injection protocol does.
+exactly as the oracle's sample-injection protocol does, or the base noise
+[K, *shape] of the last six families: uniforms in (0, 1), standard normals for HalfNormal and
+LogNormal.
 """
 from __future__ import annotations
 
@@ -25,8 +29,8 @@ import os
 from typing import Dict, Optional, Tuple
 
 import torch
-from torch.distributions import Beta, Dirichlet, Distribution, Gamma, LowRankMultivariateNormal, \
-    MultivariateNormal, Normal
+from torch.distributions import Beta, Cauchy, Dirichlet, Distribution, Exponential, Gamma, \
+    HalfCauchy, HalfNormal, Laplace, LogNormal, LowRankMultivariateNormal, MultivariateNormal, Normal
 
 from . import _native as nat
 
@@ -104,7 +108,7 @@ def _inject(cfg: DrawConfig, device: torch.device, *shape: int) -> None:
             .contiguous()
 
 
-# factors the native "mvn", "dirichlet" and "lowrank" samplers drew in the last draw_all
+# factors the native "mvn", "dirichlet", "lowrank" and "elementwise" samplers drew in the last draw_all
 # (EvidenceLowerBoundLoss.last_fusions["<family>_draws"])
 _DRAWS: "collections.Counter[str]" = collections.Counter()
 
@@ -608,6 +612,138 @@ def dirichlet_draws() -> int:
     return _DRAWS["dirichlet"]
 
 
+# ---- one-noise-word families -------------------------------------------------------------------
+# class -> MI_PRED_* code of mi_elementwise_rsample
+_ELEMENTWISE = {Exponential: nat.PRED_EXPONENTIAL, Laplace: nat.PRED_LAPLACE,
+                Cauchy: nat.PRED_CAUCHY, HalfCauchy: nat.PRED_HALF_CAUCHY,
+                HalfNormal: nat.PRED_HALF_NORMAL, LogNormal: nat.PRED_LOG_NORMAL}
+
+
+def _elementwise_arguments(distribution) -> Optional[Tuple[torch.Tensor, Optional[torch.Tensor]]]:
+    """The (a, b) parameters of mi_elementwise_rsample's table as the distribution holds them
+    (LogNormal and the half families: inside ``base_dist``), or None when they are not there."""
+    cls = type(distribution)
+    if cls is Exponential:
+        params = (getattr(distribution, "rate", None), None)
+    elif cls is Laplace or cls is Cauchy:
+        params = (getattr(distribution, "loc", None), getattr(distribution, "scale", None))
+    else:
+        base = getattr(distribution, "base_dist", None)
+        if type(base) is not (Cauchy if cls is HalfCauchy else Normal):
+            return None
+        params = (base.loc, base.scale) if cls is LogNormal else (base.scale, None)
+    if not isinstance(params[0], torch.Tensor) or \
+            not (params[1] is None or isinstance(params[1], torch.Tensor)):
+        return None
+    return params
+
+
+def native_elementwise(distribution) -> bool:
+    """
+    Whether a guide factor is drawn by mi_elementwise_rsample (and its entropy evaluated by
+    mi_elementwise_entropy): exactly an Exponential, Laplace, Cauchy, HalfCauchy, HalfNormal or
+    LogNormal (a subclass may override rsample; a TransformedDistribution spelled out by hand has
+    no entropy), float32, on the device. Any other keeps torch's own rsample and entropy.
+    """
+    if type(distribution) not in _ELEMENTWISE:
+        return False
+    params = _elementwise_arguments(distribution)
+    return params is not None and all(t is None or (t.is_cuda and t.dtype == torch.float32)
+                                      for t in params)
+
+
+def _elementwise_params(distribution, N: int):
+    """(family, a, a stride, b or None, b stride) of a :func:`native_elementwise` factor viewed
+    as [N]; a deferred exp transform of a positive parameter runs first."""
+    a, b = _elementwise_arguments(distribution)
+    fill_exp(a)
+    a, a_s = _flat_param(a, N)
+    b_s = 0
+    if b is not None:
+        fill_exp(b)
+        b, b_s = _flat_param(b, N)
+    return _ELEMENTWISE[type(distribution)], a, a_s, b, b_s
+
+
+class _ElementwiseRsampleFn(torch.autograd.Function):
+    """
+    rsample of the one-noise-word families over K particles by mi_elementwise_rsample; the backward
+    regenerates the noise (mi_elementwise_rsample_backward). ``cfg.noise`` injects the base noise
+    [K, N]: uniforms, or standard normals for HalfNormal and LogNormal.
+    """
+    @staticmethod
+    def forward(ctx, cfg: DrawConfig, family: int, a: torch.Tensor, a_s: int,
+                b: Optional[torch.Tensor], b_s: int):  # type: ignore[override]
+        N, K = a.shape[0], cfg.K
+        z = torch.empty((K, N), dtype=torch.float32, device=a.device)
+        seed, step = _philox_key(cfg)
+        nat.check(nat.lib().mi_elementwise_rsample(
+            family, a.data_ptr(), a_s, nat.ptr(b), b_s, K, N, seed, step,
+            nat.ptr(cfg.step_device), cfg.stream_id, cfg.particle_offset, nat.ptr(cfg.noise),
+            z.data_ptr(), nat.stream_handle(a.device)), "mi_elementwise_rsample")
+        ctx.cfg, ctx.family, ctx.strides, ctx.N = cfg, family, (a_s, b_s), N
+        ctx.save_for_backward(a, b)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz: torch.Tensor):  # type: ignore[override]
+        cfg: DrawConfig = ctx.cfg
+        a, b = ctx.saved_tensors
+        (a_s, b_s), N, K = ctx.strides, ctx.N, cfg.K
+        device, dz = dz.device, _float32(dz)
+        need_a = ctx.needs_input_grad[2]
+        need_b = b is not None and ctx.needs_input_grad[4]
+        if not (need_a or need_b):
+            return None, None, None, None, None, None
+        workspace, size = _workspace("mi_elementwise_rsample_backward_workspace_bytes", K, N,
+                                     device=device)
+        da = torch.empty(N, dtype=torch.float32, device=device) if need_a else None
+        db = torch.empty(N, dtype=torch.float32, device=device) if need_b else None
+        seed, step = _philox_key(cfg)
+        nat.check(nat.lib().mi_elementwise_rsample_backward(
+            ctx.family, dz.data_ptr(), dz.stride(0), dz.stride(1), a.data_ptr(), a_s, nat.ptr(b),
+            b_s, K, N, seed, step, nat.ptr(backward_step(cfg)), cfg.stream_id,
+            cfg.particle_offset, nat.ptr(cfg.noise), workspace.data_ptr(), size, nat.ptr(da),
+            nat.ptr(db), nat.stream_handle(device)), "mi_elementwise_rsample_backward")
+        # per element; a broadcast parameter's expand backward sums them
+        return None, None, da, None, db, None
+
+
+class _ElementwiseEntropyFn(torch.autograd.Function):
+    """entropy().sum() of a one-noise-word factor and its gradient in one launch
+    (mi_elementwise_entropy); the backward scales the stored gradient."""
+    @staticmethod
+    def forward(ctx, family: int, a: torch.Tensor, a_s: int, b: Optional[torch.Tensor],
+                b_s: int):  # type: ignore[override]
+        N = a.shape[0]
+        out = torch.empty((), dtype=torch.float32, device=a.device)
+        # (the entropy of a Laplace or Cauchy factor does not depend on its loc)
+        da = torch.empty(N, dtype=torch.float32, device=a.device) if ctx.needs_input_grad[1] and \
+            family not in (nat.PRED_LAPLACE, nat.PRED_CAUCHY) else None
+        db = torch.empty(N, dtype=torch.float32, device=a.device) if b is not None and \
+            ctx.needs_input_grad[3] else None
+        nat.check(nat.lib().mi_elementwise_entropy(
+            family, a.data_ptr(), a_s, nat.ptr(b), b_s, N, out.data_ptr(), nat.ptr(da),
+            nat.ptr(db), nat.stream_handle(a.device)), "mi_elementwise_entropy")
+        ctx.grads = (da, db)
+        return out
+
+    @staticmethod
+    def backward(ctx, g: torch.Tensor):  # type: ignore[override]
+        da, db = ctx.grads
+        return None, None if da is None else da * g, None, None if db is None else db * g, None
+
+
+def elementwise_entropy(distribution) -> torch.Tensor:
+    """The summed entropy of a :func:`native_elementwise` guide factor (0-d, differentiable)."""
+    N = max(1, int(distribution.batch_shape.numel()))
+    return _ElementwiseEntropyFn.apply(*_elementwise_params(distribution, N))
+
+
+def elementwise_draws() -> int:
+    return _DRAWS["elementwise"]
+
+
 # ---- deferred small Normal draws ---------------------------------------------------------------
 # A small Normal factor's [K, N] draw (the regression's theta, N = P features) is made by the loss's
 # planning instead of when the guide is drawn: when the only kernel that reads it is one linear
@@ -924,6 +1060,14 @@ def draw(distribution: Distribution, cfg: DrawConfig, lazy: bool = False) -> tor
         _inject(cfg, loc.device, D + R)   # eps_D | eps_W, [K, D + R]
         _DRAWS["lowrank"] += 1
         return _LowRankRsampleFn.apply(cfg, loc, cov_factor.contiguous(), cov_diag.contiguous())
+    if native_elementwise(distribution):
+        shape = distribution.batch_shape
+        N = max(1, int(shape.numel()))
+        family, a, a_s, b, b_s = _elementwise_params(distribution, N)
+        _inject(cfg, a.device, N)   # base noise (uniforms or normals), [K, *shape]
+        _DRAWS["elementwise"] += 1
+        z = _ElementwiseRsampleFn.apply(cfg, family, a, a_s, b, b_s)
+        return z.reshape((cfg.K,) + tuple(shape))
     if cfg.noise is not None:
         return cfg.noise
     return distribution.rsample(torch.Size([cfg.K]))

@@ -468,14 +468,18 @@ class EvidenceLowerBoundLoss(nn.Module):
     Guide factors of type Normal, Beta, Gamma, MultivariateNormal (unbatched, float32, on the
     device, at most 1024 dimensions; any of its three parameterisations), Dirichlet (float32, on
     the device, at most 1024 categories) and LowRankMultivariateNormal (unbatched, float32, on the
-    device, rank at most 128, at most 2**24 dimensions) are drawn by the native samplers: ``seed``
+    device, rank at most 128, at most 2**24 dimensions), and Exponential, Laplace, Cauchy,
+    HalfCauchy, HalfNormal and LogNormal (exactly those classes, float32, on the device) are drawn
+    by the native samplers: ``seed``
     governs their draws, particle shards draw the union of what one device would draw, and a
     captured step draws anew on every replay. Their entropy is evaluated inside the ELBO kernels
-    (Dirichlet: by its own kernel, ``mi_dirichlet_entropy``; LowRankMultivariateNormal: by torch's
+    (Dirichlet: by its own kernel, ``mi_dirichlet_entropy``; the last six: by
+    ``mi_elementwise_entropy``; LowRankMultivariateNormal: by torch's
     own ``entropy``). Every other factor uses its own ``rsample`` (torch's generator) and
     ``entropy``. ``last_fusions`` reports the fast paths the last evaluation took, among them
-    ``mvn_draws``, ``dirichlet_draws`` and ``lowrank_draws``, the numbers of factors the native
-    MultivariateNormal, Dirichlet and LowRankMultivariateNormal samplers drew.
+    ``mvn_draws``, ``dirichlet_draws``, ``lowrank_draws`` and ``elementwise_draws``, the numbers of
+    factors the native MultivariateNormal, Dirichlet, LowRankMultivariateNormal and one-noise-word
+    samplers drew.
 
     Example:
 
@@ -656,9 +660,11 @@ class EvidenceLowerBoundLoss(nn.Module):
                 guide.release_lazy()
             if rest:
                 names = {id(f): name for name, f in approximation.items()}
-                # (a native Dirichlet factor: value and gradient by mi_dirichlet_entropy)
+                # (a native Dirichlet factor: value and gradient by mi_dirichlet_entropy; a
+                # native one-noise-word factor: by mi_elementwise_entropy)
                 extra = cast(torch.Tensor, sum(
                     (guide.dirichlet_entropy(f) if guide.native_dirichlet(f)
+                     else guide.elementwise_entropy(f) if guide.native_elementwise(f)
                      else f.entropy().sum()) /
                     (world if shared is None or names[id(f)] in shared else 1)
                     for f in rest))
