@@ -9,78 +9,14 @@ transposed theta.
 Tolerances: totals 1e-5 relative (the north-star ELBO tolerance); gradients 1e-5 relative of the
 sum of |terms|, since they are sums of terms of both signs.
 """
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
 from mininf_amd import _native as nat
+from tests.linear_reference import reference, run
 
 pytestmark = pytest.mark.gpu
-
-
-def reference(family, X, theta, y, mask, sigma, site_scale, g0):
-    X64, th = X.astype(np.float64), theta.astype(np.float64)
-    mu = X64 @ th.T                                   # [N, K]
-    m = mask.astype(np.float64)[:, None]
-    y64 = np.where(mask, y, 0.0).astype(np.float64)[:, None]   # masked lanes are never read
-    if family == nat.NORMAL:
-        s = sigma.astype(np.float64)[None, :]
-        d = y64 - mu
-        lp = -d ** 2 / (2 * s ** 2) - np.log(s) - 0.5 * np.log(2 * np.pi)
-        dmu = d / s ** 2
-        dsig = d ** 2 / s ** 3 - 1 / s
-    else:
-        lp = y64 * mu - np.logaddexp(0.0, mu)
-        dmu = y64 - 1 / (1 + np.exp(-mu))
-        dsig = np.zeros_like(mu)
-    total = site_scale * (m * lp).sum(0)
-    dtheta = g0 * site_scale * ((m * dmu).T @ X64)    # [K, P]
-    dsigma = g0 * site_scale * (m * dsig).sum(0)
-    bound = site_scale * (np.abs(m * dmu).T @ np.abs(X64)) + 1e-6
-    sbound = site_scale * np.abs(m * dsig).sum(0) + 1e-6
-    return total, dtheta, dsigma, bound, sbound
-
-
-def run(family, X, theta, y, mask, sigma, sigma_per_particle, site_scale, g0, valu):
-    device = X.device
-    N, P = X.shape
-    K = theta.shape[0]
-    L = nat.Linear()
-    L.K, L.N, L.P = K, N, P
-    L.family = family
-    L.options = nat.LINEAR_VALU if valu else 0
-    L.x = X.data_ptr()
-    L.x_stride_i, L.x_stride_j = X.stride()
-    L.theta = theta.data_ptr()
-    L.theta_stride_k, L.theta_stride_j = theta.stride()
-    L.value = y.data_ptr()
-    L.value_stride_i = y.stride(0)
-    if mask is not None:
-        L.mask = mask.data_ptr()
-        L.mask_stride_i = mask.stride(0)
-    if sigma_per_particle:
-        L.scale = sigma.data_ptr()
-        L.scale_stride_k = sigma.stride(0)
-    else:
-        L.scale_constant = float(sigma[0])
-    L.grad_scale = g0
-    L.site_scale = site_scale
-    L.compute_grads = 1
-    lib = nat.lib()
-    size = ctypes.c_size_t()
-    nat.check(lib.mi_linear_workspace_bytes(ctypes.byref(L), ctypes.byref(size)), "workspace")
-    work = torch.empty(size.value, dtype=torch.uint8, device=device)
-    total = torch.empty(K, device=device)
-    nslots = P + (1 if sigma_per_particle else 0)
-    dslots = torch.empty((nslots, K), device=device)
-    flags = torch.empty(1, dtype=torch.int32, device=device)
-    nat.check(lib.mi_linear_forward(ctypes.byref(L), work.data_ptr(), size.value, total.data_ptr(),
-                                    dslots.data_ptr(), flags.data_ptr(),
-                                    nat.stream_handle(device)), "mi_linear_forward")
-    torch.cuda.synchronize()
-    return total.cpu().numpy(), dslots.cpu().numpy(), int(flags.cpu()[0])
 
 
 CASES = [
