@@ -494,6 +494,29 @@ int mi_lowrank_rsample_backward(const float* dz, int64_t dz_stride_k, int64_t dz
                                 void* workspace, size_t workspace_bytes, float* dloc,
                                 float* dcov_factor, float* dcov_diag, void* stream);
 
+/* Entropy of the same factor (replaces LowRankMultivariateNormal.entropy, torch 2.10
+ * lowrank_multivariate_normal.py:225-237) and its gradient in closed form, from row-major
+ * contiguous W = cov_factor[D, R], d = cov_diag[D] and L = capacitance_tril[R, R], the lower
+ * Cholesky factor of C = I + W^T diag(1 / d) W that the constructor keeps as _capacitance_tril
+ * (only its lower triangle is read). With M = W C^-1:
+ *   entropy           = 0.5 D (1 + log 2 pi) + sum_j log L[j, j] + 0.5 sum_i log d[i]
+ *   dcov_factor[i, r] = M[i, r] / d[i]
+ *   dcov_diag[i]      = 0.5 (1 / d[i] - (sum_r M[i, r] W[i, r]) / d[i]^2)
+ * the whole derivative with respect to W and d, L's dependence on them included: nothing is to be
+ * propagated through L. Three launches: L^-1 and C^-1 in fp64 by one workgroup (C^-1 handed on as
+ * f32), one pass over W (on v_mfma_f32_32x32x2_f32 for R >= 32; W read once, dcov_factor written
+ * once), and the log sums combined in fp64 in a fixed order (no atomics: two calls on the same
+ * inputs are bit-identical). dcov_factor and dcov_diag may both be NULL: only the value is
+ * computed, bit-identical to the one computed with them. The caps are the draw's (beyond them:
+ * MI_EUNSUPPORTED); D < 1, R < 1, a NULL required pointer, one gradient pointer without the other
+ * or a workspace smaller than mi_lowrank_entropy_workspace_bytes asks for: MI_EINVAL. All checked
+ * before any device work. */
+int mi_lowrank_entropy_workspace_bytes(int64_t D, int64_t R, size_t* bytes);
+int mi_lowrank_entropy(const float* cov_factor, const float* cov_diag,
+                       const float* capacitance_tril, int64_t D, int64_t R,
+                       void* workspace, size_t workspace_bytes,
+                       float* entropy, float* dcov_factor, float* dcov_diag, void* stream);
+
 /* Beta(concentration1, concentration0) draws x[k, i] = G1 / (G1 + G0) with Marsaglia-Tsang gamma
  * variates from the same counter-based generator (beta.py:85-86, dirichlet.py:23-36, 85-88). With
  * `x_in` non-NULL the draws are copied from it instead (parity mode). */

@@ -295,6 +295,10 @@ _SIGNATURES = {
                                                    ctypes.c_uint64, ctypes.c_uint64, c_vp,
                                                    ctypes.c_uint32, c_i64, c_vp, c_vp,
                                                    ctypes.c_size_t, c_vp, c_vp, c_vp, c_vp]),
+    "mi_lowrank_entropy_workspace_bytes": (ctypes.c_int, [
+        c_i64, c_i64, ctypes.POINTER(ctypes.c_size_t)]),
+    "mi_lowrank_entropy": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, ctypes.c_size_t,
+                                          c_vp, c_vp, c_vp, c_vp]),
     "mi_beta_rsample": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, ctypes.c_uint64,
                                        ctypes.c_uint64, c_vp, ctypes.c_uint32, c_i64, c_vp, c_vp,
                                        c_vp]),

@@ -1923,7 +1923,9 @@ class _ElboPlan:
         lowrank_draws: LowRankMultivariateNormal guide factors drawn by the native sampler
         (mi_lowrank_rsample); elementwise_draws: Exponential, Laplace, Cauchy, HalfCauchy,
         HalfNormal and LogNormal guide factors drawn by the native sampler
-        (mi_elementwise_rsample).
+        (mi_elementwise_rsample); lowrank_entropies: LowRankMultivariateNormal guide factors whose
+        entropy and its gradient the native kernel evaluated (mi_lowrank_entropy, called by the
+        loss after this plan ran).
         """
         return {
             "folded_priors": sum(l.prior is not None for l in self.launchers) +
@@ -1940,6 +1942,7 @@ class _ElboPlan:
             "dirichlet_draws": guide.dirichlet_draws(),
             "lowrank_draws": guide.lowrank_draws(),
             "elementwise_draws": guide.elementwise_draws(),
+            "lowrank_entropies": 0,   # set by the loss, which evaluates the rest's entropies
         }
 
     def _reduce_ok(self, assume=None) -> bool:
@@ -2324,10 +2327,10 @@ def entropy_factors(approximation) -> Tuple[List[EntropyFactor], list]:
     Split a factorised guide into factors whose entropy the ELBO kernels evaluate (Normal, Beta,
     Gamma) and the rest (whose entropy torch.distributions evaluates, or -- a native Dirichlet
     factor, guide.native_dirichlet -- mi_dirichlet_entropy, or -- a native one-noise-word factor,
-    guide.native_elementwise -- mi_elementwise_entropy, both called by the loss). A
-    LowRankMultivariateNormal factor stays in the rest also when its draws are native
-    (guide.native_lowrank): its entropy is torch's, and with it the loss is no longer the fused
-    node alone, so its gradients take autograd, never the direct-to-leaf paths.
+    guide.native_elementwise -- mi_elementwise_entropy, or -- a native LowRankMultivariateNormal
+    factor, guide.native_lowrank -- mi_lowrank_entropy, all called by the loss). With a factor in
+    the rest the loss is no longer the fused node alone, so its gradients take autograd, never the
+    direct-to-leaf paths.
     """
     from torch.distributions import Beta, Gamma, Normal
 

@@ -466,10 +466,10 @@ def mvn_draws() -> int:
 
 def native_lowrank(distribution) -> bool:
     """
-    Whether a LowRankMultivariateNormal guide factor is drawn by mi_lowrank_rsample: exactly that
-    class (a subclass may override rsample), unbatched, float32, on the device,
-    R <= MI_LOWRANK_MAX_R and D <= MI_LOWRANK_MAX_D. Any other keeps torch's own rsample. The
-    entropy is torch's in either case.
+    Whether a LowRankMultivariateNormal guide factor is drawn by mi_lowrank_rsample (and its
+    entropy evaluated by mi_lowrank_entropy): exactly that class (a subclass may override rsample
+    or entropy), unbatched, float32, on the device, R <= MI_LOWRANK_MAX_R and
+    D <= MI_LOWRANK_MAX_D. Any other keeps torch's own rsample and entropy.
     """
     if type(distribution) is not LowRankMultivariateNormal or \
             tuple(distribution.batch_shape) != ():
@@ -527,6 +527,56 @@ class _LowRankRsampleFn(torch.autograd.Function):
 
 def lowrank_draws() -> int:
     return _DRAWS["lowrank"]
+
+
+class _LowRankEntropyFn(torch.autograd.Function):
+    """
+    LowRankMultivariateNormal.entropy() (lowrank_multivariate_normal.py:225-237) and its gradient
+    with respect to cov_factor and cov_diag in closed form, in one mi_lowrank_entropy call; the
+    backward scales the stored gradients. ``tril`` is the factor's _capacitance_tril, detached:
+    the closed form carries its whole dependence on the two parameters.
+    """
+    @staticmethod
+    def forward(ctx, cov_factor: torch.Tensor, cov_diag: torch.Tensor,
+                tril: torch.Tensor):  # type: ignore[override]
+        D, R = cov_factor.shape
+        device = cov_factor.device
+        out = torch.empty((), dtype=torch.float32, device=device)
+        grads = cov_factor.requires_grad or cov_diag.requires_grad
+        dfactor = torch.empty_like(cov_factor) if grads else None
+        ddiag = torch.empty_like(cov_diag) if grads else None
+        workspace, size = _workspace("mi_lowrank_entropy_workspace_bytes", D, R, device=device)
+        nat.check(nat.lib().mi_lowrank_entropy(
+            cov_factor.data_ptr(), cov_diag.data_ptr(), tril.data_ptr(), D, R,
+            workspace.data_ptr(), size, out.data_ptr(), nat.ptr(dfactor), nat.ptr(ddiag),
+            nat.stream_handle(device)), "mi_lowrank_entropy")
+        ctx.grads = (dfactor, ddiag)
+        return out
+
+    @staticmethod
+    def backward(ctx, g: torch.Tensor):  # type: ignore[override]
+        dfactor, ddiag = ctx.grads
+        if dfactor is None:
+            return None, None, None
+        return dfactor * g, ddiag * g, None
+
+
+def lowrank_entropy(distribution: LowRankMultivariateNormal) -> torch.Tensor:
+    """The entropy of a :func:`native_lowrank` guide factor (0-d, differentiable with respect to
+    cov_factor and cov_diag; nothing flows into the constructor's capacitance graph)."""
+    cov_factor = distribution._unbroadcasted_cov_factor
+    cov_diag = distribution._unbroadcasted_cov_diag
+    fill_exp(cov_diag)
+    tril = distribution._capacitance_tril.detach()
+    _DRAWS["lowrank_entropy"] += 1
+    return _LowRankEntropyFn.apply(cov_factor.contiguous(), cov_diag.contiguous(),
+                                   tril.contiguous())
+
+
+def lowrank_entropies() -> int:
+    """LowRankMultivariateNormal factors whose entropy mi_lowrank_entropy evaluated since the last
+    draw_all (EvidenceLowerBoundLoss.last_fusions["lowrank_entropies"])."""
+    return _DRAWS["lowrank_entropy"]
 
 
 def native_dirichlet(distribution) -> bool:

@@ -474,12 +474,14 @@ class EvidenceLowerBoundLoss(nn.Module):
     governs their draws, particle shards draw the union of what one device would draw, and a
     captured step draws anew on every replay. Their entropy is evaluated inside the ELBO kernels
     (Dirichlet: by its own kernel, ``mi_dirichlet_entropy``; the last six: by
-    ``mi_elementwise_entropy``; LowRankMultivariateNormal: by torch's
-    own ``entropy``). Every other factor uses its own ``rsample`` (torch's generator) and
+    ``mi_elementwise_entropy``; LowRankMultivariateNormal: by ``mi_lowrank_entropy``, value and
+    closed-form gradient from the constructor's ``_capacitance_tril``, nothing propagated through
+    the constructor). Every other factor uses its own ``rsample`` (torch's generator) and
     ``entropy``. ``last_fusions`` reports the fast paths the last evaluation took, among them
     ``mvn_draws``, ``dirichlet_draws``, ``lowrank_draws`` and ``elementwise_draws``, the numbers of
     factors the native MultivariateNormal, Dirichlet, LowRankMultivariateNormal and one-noise-word
-    samplers drew.
+    samplers drew, and ``lowrank_entropies``, the number of factors whose entropy
+    ``mi_lowrank_entropy`` evaluated.
 
     Example:
 
@@ -661,13 +663,13 @@ class EvidenceLowerBoundLoss(nn.Module):
             if rest:
                 names = {id(f): name for name, f in approximation.items()}
                 # (a native Dirichlet factor: value and gradient by mi_dirichlet_entropy; a
-                # native one-noise-word factor: by mi_elementwise_entropy)
+                # native one-noise-word factor: by mi_elementwise_entropy; a native
+                # LowRankMultivariateNormal factor: by mi_lowrank_entropy)
                 extra = cast(torch.Tensor, sum(
-                    (guide.dirichlet_entropy(f) if guide.native_dirichlet(f)
-                     else guide.elementwise_entropy(f) if guide.native_elementwise(f)
-                     else f.entropy().sum()) /
+                    _rest_entropy(f) /
                     (world if shared is None or names[id(f)] in shared else 1)
                     for f in rest))
+                self.last_fusions["lowrank_entropies"] = guide.lowrank_entropies()
                 engine.flush_pending_step()
                 loss = loss - extra
             if loss.is_cuda and loss.dim() == 0 and type(loss) is torch.Tensor:
@@ -685,6 +687,18 @@ class EvidenceLowerBoundLoss(nn.Module):
             else:
                 joint.raise_on_violation()
         return loss
+
+
+def _rest_entropy(factor: torch.distributions.Distribution) -> torch.Tensor:
+    """The summed entropy of a guide factor the ELBO kernels do not evaluate
+    (engine.entropy_factors' rest): by the family's own kernel where it has one, else torch's."""
+    if guide.native_dirichlet(factor):
+        return guide.dirichlet_entropy(factor)
+    if guide.native_elementwise(factor):
+        return guide.elementwise_entropy(factor)
+    if guide.native_lowrank(factor):
+        return guide.lowrank_entropy(factor)
+    return factor.entropy().sum()
 
 
 def _guide_device(approximation: Dict[str, torch.distributions.Distribution]) -> torch.device:

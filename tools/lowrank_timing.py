@@ -1,8 +1,11 @@
 """
-Time a LowRankMultivariateNormal guide: an eager ELBO evaluation and its backward of
-`theta ~ Normal(0, 1)` with D elements, K = 256, R = 16, natively drawn against torch's own rsample
-(the same code with guide.native_lowrank declining), variants alternating in one process, device
-events; and mi_lowrank_rsample + mi_lowrank_rsample_backward alone. Prints one JSON line per D.
+Time a LowRankMultivariateNormal guide: an eager ELBO evaluation and its backward
+of `theta ~ Normal(0, 1)` with D elements, K = 256, R = 16, natively drawn and its entropy native
+("native"), natively drawn with torch's own entropy ("torch_entropy": the same code with
+guide.lowrank_entropy replaced by torch's), and torch's own rsample and entropy ("torch": the same
+code with guide.native_lowrank declining), variants alternating in one process, device events; and
+mi_lowrank_rsample, mi_lowrank_rsample_backward and mi_lowrank_entropy (value and gradients)
+alone. Prints one JSON line per D.
 """
 import argparse
 import ctypes
@@ -67,7 +70,19 @@ def launches(D, R, K, device):
             dz.data_ptr(), D, 1, d.data_ptr(), K, D, R, 1, 0, None, 0, 0, None, ws.data_ptr(),
             size.value, dloc.data_ptr(), dW.data_ptr(), dd.data_ptr(), None), "backward")
 
-    return forward, backward
+    tril = torch.linalg.cholesky(torch.eye(R, device=device) + W.T @ (W / d[:, None]))
+    entropy_size = ctypes.c_size_t()
+    nat.check(lib.mi_lowrank_entropy_workspace_bytes(D, R, ctypes.byref(entropy_size)), "ws")
+    esize = entropy_size.value
+    ews = torch.empty(esize, dtype=torch.uint8, device=device)
+    H = torch.empty((), device=device)
+
+    def entropy():
+        nat.check(lib.mi_lowrank_entropy(
+            W.data_ptr(), d.data_ptr(), tril.data_ptr(), D, R, ews.data_ptr(), esize, H.data_ptr(),
+            dW.data_ptr(), dd.data_ptr(), None), "entropy")
+
+    return forward, backward, entropy
 
 
 def main():
@@ -79,11 +94,19 @@ def main():
     parser.add_argument("--steps", type=int, default=20)
     args = parser.parse_args()
     device = torch.device("cuda")
-    native_lowrank = guide.native_lowrank
+    native_lowrank, lowrank_entropy = guide.native_lowrank, guide.lowrank_entropy
     for D in args.sizes:
         R, K = args.rank, args.particles
         native, native_loss = elbo_step(D, R, K, device)
         torch_path, torch_loss = elbo_step(D, R, K, device)
+        entropy_path, entropy_loss = elbo_step(D, R, K, device)
+
+        def torch_entropy():   # the native draw with the entropy autograd walks the constructor for
+            guide.lowrank_entropy = lambda distribution: distribution.entropy().sum()
+            try:
+                return entropy_path()
+            finally:
+                guide.lowrank_entropy = lowrank_entropy
 
         def declined():
             guide.native_lowrank = lambda distribution: False
@@ -92,21 +115,28 @@ def main():
             finally:
                 guide.native_lowrank = native_lowrank
 
-        for fn in (native, declined):
+        for fn in (native, torch_entropy, declined):
             timed(fn, 10)
         assert native_loss.last_fusions["lowrank_draws"] == 1
+        assert native_loss.last_fusions["lowrank_entropies"] == 1
+        assert entropy_loss.last_fusions["lowrank_draws"] == 1
+        assert entropy_loss.last_fusions["lowrank_entropies"] == 0
         assert torch_loss.last_fusions["lowrank_draws"] == 0
-        times = {"native": [], "torch": []}
+        assert torch_loss.last_fusions["lowrank_entropies"] == 0
+        times = {"native": [], "torch_entropy": [], "torch": []}
         for _ in range(args.rounds):
             times["native"].append(timed(native, args.steps))
+            times["torch_entropy"].append(timed(torch_entropy, args.steps))
             times["torch"].append(timed(declined, args.steps))
-        forward, backward = launches(D, R, K, device)
-        for fn in (forward, backward):
+        forward, backward, entropy = launches(D, R, K, device)
+        for fn in (forward, backward, entropy):
             timed(fn, 10)
         fwd = [timed(forward, 50) for _ in range(10)]
         bwd = [timed(backward, 50) for _ in range(10)]
+        ent = [timed(entropy, 50) for _ in range(10)]
         row = {"D": D, "R": R, "K": K}
-        for name, values in (*times.items(), ("forward_launch", fwd), ("backward_launch", bwd)):
+        for name, values in (*times.items(), ("forward_launch", fwd), ("backward_launch", bwd),
+                             ("entropy_launch", ent)):
             row[name + "_ms"] = {"median": round(statistics.median(values), 4),
                                  "min": round(min(values), 4), "max": round(max(values), 4)}
         # the forward against writing z once: 4 K D bytes
