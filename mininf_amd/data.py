@@ -28,13 +28,13 @@ the same.) Sites evaluated by the kernels flag values of the rows they read, as 
 """
 from __future__ import annotations
 
-import os
 import weakref
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
 from . import _native as nat
+from . import switches
 
 _functorch = torch._C._functorch
 
@@ -96,7 +96,7 @@ class _Batch:
         they are drawn already. The caller launches it next, or calls :meth:`draw_rows` first.
         """
         if not self.pending or self.count != self.loader.batch_size or \
-                os.environ.get("MININF_AMD_FUSE_ROWS", "1") == "0":
+                not switches.enabled("FUSE_ROWS"):
             return None
         loader = self.loader
         R = nat.Rows()

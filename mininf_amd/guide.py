@@ -25,7 +25,6 @@ from __future__ import annotations
 import collections
 import ctypes
 import dataclasses
-import os
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -33,6 +32,7 @@ from torch.distributions import Beta, Cauchy, Dirichlet, Distribution, Exponenti
     HalfCauchy, HalfNormal, Laplace, LogNormal, LowRankMultivariateNormal, MultivariateNormal, Normal
 
 from . import _native as nat
+from . import switches
 
 
 @dataclasses.dataclass
@@ -122,7 +122,7 @@ class _NormalRsampleFn(torch.autograd.Function):
         z = torch.empty((K, N), dtype=torch.float32, device=loc.device)
         draw = PendingDraw(cfg, z, loc, loc_s, scale, scale_s, exp_source(scale))
         if cfg.defer and cfg.noise is None and (N % 4 == 0 or N == 1) and N <= DEFER_MAX_N and \
-                os.environ.get("MININF_AMD_DRAW_IN_LINEAR", "1") != "0":
+                switches.enabled("DRAW_IN_LINEAR"):
             _PENDING_DRAWS[_storage_of(z)] = draw   # launched by flush_draws, or taken
         else:
             draw.launch()
@@ -973,7 +973,7 @@ def _beta_dgrad(x: torch.Tensor, conc: torch.Tensor, K: int, N: int) -> Optional
     cost more per node than the overlap saved (0.17 -> 0.24 ms per step).
     """
     if not (torch.is_grad_enabled() and conc.requires_grad) or K * N > BETA_DGRAD_MAX or \
-            os.environ.get("MININF_AMD_BETA_DGRAD", "0") != "1":
+            not switches.enabled("BETA_DGRAD", default=False):
         return None
     main = torch.cuda.current_stream()
     side = _side_stream(x.device)
@@ -1031,7 +1031,7 @@ def lazy_of(tensor) -> Optional[LazyDraw]:
 def _fusable_normal(distribution: Normal, N: int) -> bool:
     return (N >= 512 and N % 4 == 0 and distribution.loc.is_cuda and
             distribution.loc.dtype == torch.float32 and distribution.scale.dtype == torch.float32
-            and os.environ.get("MININF_AMD_FUSE_DRAWS", "1") != "0")
+            and switches.enabled("FUSE_DRAWS"))
 
 
 def draw(distribution: Distribution, cfg: DrawConfig, lazy: bool = False) -> torch.Tensor:

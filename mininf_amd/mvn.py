@@ -15,13 +15,13 @@ The density is an ``autograd.Function`` with a vmap rule: inside the particle tr
 from __future__ import annotations
 
 import math
-import os
 from typing import Tuple
 
 import torch
 from torch.distributions import MultivariateNormal
 
 from . import _native as nat
+from . import switches
 
 MAX_N = 1024   # MI_MVN_MAX_N
 
@@ -29,7 +29,7 @@ MAX_N = 1024   # MI_MVN_MAX_N
 def enabled(distribution: MultivariateNormal) -> bool:
     """Whether ``distribution``'s density runs on the kernel (float64 on the device, n <= MAX_N)."""
     L = distribution._unbroadcasted_scale_tril
-    return os.environ.get("MININF_AMD_MVN_KERNEL", "1") != "0" and L.dtype == torch.float64 \
+    return switches.enabled("MVN_KERNEL") and L.dtype == torch.float64 \
         and L.device.type == "cuda" and 1 <= L.shape[-1] <= MAX_N
 
 
@@ -160,7 +160,7 @@ def cholesky_ex(A: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
 
 
 def cholesky_supported(A: torch.Tensor) -> bool:
-    return os.environ.get("MININF_AMD_CHOLESKY_KERNEL", "1") != "0" and A.is_cuda and \
+    return switches.enabled("CHOLESKY_KERNEL") and A.is_cuda and \
         A.dtype in (torch.float32, torch.float64) and A.dim() >= 2 and \
         A.shape[-1] == A.shape[-2] and 1 <= A.shape[-1] <= MAX_N
 

@@ -15,14 +15,13 @@ estimates. The returned loss is a 0-d float32 tensor with ``grad_fn``.
 from __future__ import annotations
 
 import ctypes
-import os
 import struct
 from typing import Callable, cast, Dict, Optional, Set, Type
 
 import torch
 from torch import distributions, nn
 
-from . import _native, engine, graph, guide, linear, particles
+from . import _native, engine, graph, guide, linear, particles, switches
 from .core import condition, LogProbTracer
 from .util import _normalize_shape, maybe_as_tensor, OptionalSize, TensorDict
 
@@ -246,7 +245,7 @@ def _float32(value: float) -> float:
 
 def _defer_exp() -> bool:
     """Whether guide exp transforms are left to the draws that read them (MININF_AMD_DEFER_EXP)."""
-    return os.environ.get("MININF_AMD_DEFER_EXP", "1") != "0"
+    return switches.enabled("DEFER_EXP")
 
 
 class _ExpFn(torch.autograd.Function):
@@ -401,7 +400,7 @@ def _accumulate_final_grads(loss: torch.Tensor, unit: torch.Tensor) -> bool:
     tensor_inputs = getattr(plan, "tensor_inputs", None)
     if plan is None or getattr(plan, "final", None) is None or plan.state is None or \
             tensor_inputs is None or loss._backward_hooks or loss.retains_grad or \
-            os.environ.get("MININF_AMD_DIRECT_GRADS", "1") == "0":
+            not switches.enabled("DIRECT_GRADS"):
         return False
     if torch.distributed.is_available() and torch.distributed.is_initialized():
         return False

@@ -23,7 +23,6 @@ import contextlib
 import copy
 import dataclasses
 import hashlib
-import os
 import weakref
 from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, cast
 
@@ -38,7 +37,7 @@ from torch.distributions.utils import lazy_property
 from torch.overrides import TorchFunctionMode
 from torch.utils._pytree import tree_flatten, tree_map
 
-from . import _native, core, data, graph, mvn, predictive
+from . import _native, core, data, graph, mvn, predictive, switches
 from .distributions import InverseGamma
 from .core import batch, no_log_prob, State, TracerMixin, Value, validate_shape
 from .util import _normalize_shape, check_constraint, OptionalSize
@@ -719,7 +718,7 @@ def _trace(model: Callable, samples: Dict[str, torch.Tensor], K: int, validate: 
     from .linear import DeferredMatmul
 
     if defer_matmul is None:
-        defer_matmul = os.environ.get("MININF_AMD_DEFER_MATMUL", "1") != "0"
+        defer_matmul = switches.enabled("DEFER_MATMUL")
     names = list(samples)
     tracer = ParticleTracer(validate=validate)
 

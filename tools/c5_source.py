@@ -1,6 +1,6 @@
 """
 Write the specialised site program of the C5 group (the fused z draw with the z / y / b sites,
-engine.describe's layout) to a file, on the CPU: mi_group_source is host code. Compile the result
+the layout of engine._GroupLauncher.describe) to a file, on the CPU: mi_group_source is host code. Compile the result
 offline to inspect its ISA, e.g.
 
     python tools/c5_source.py /tmp/c5.hip [K] [N]

@@ -56,10 +56,13 @@ def main():
     wrap(engine, "entropy_factors", "loss.entropy_factors")
     wrap(engine._ElboPlan, "backward", "backward.elbo_plan")
     if os.environ.get("DEEP", "0") != "0":   # finer phases (each wrapper adds ~0.3 us)
+        # a function is wrapped in the module whose code calls it by bare name
         for module, names in (
                 (engine, ("_lazy_uses", "claim_linear_draws", "plan_linear", "fold_priors",
-                          "fold_linear_priors", "release_unsafe_claims", "_to_device", "_collapse",
-                          "_defer_step", "_elbo_workspace", "_run_categorical")),
+                          "fold_linear_priors", "release_unsafe_claims")),
+                (engine._plan, ("_to_device", "_collapse")),
+                (engine._elbo_plan, ("_defer_step", "_elbo_workspace")),
+                (engine._rows, ("_run_categorical",)),
                 (engine._GroupLauncher, ("run", "try_add", "shares_dense_operand", "__init__")),
                 (engine._ElboPlan, ("__init__", "inputs", "_describe", "_describe_absorbed",
                                     "fusions", "_elbo_adam", "_factor_grads", "_reduce_ok",
