@@ -374,6 +374,40 @@ int mi_dirichlet_forward(const float* concentration, int64_t stride_k, int64_t s
                          size_t workspace_bytes, float* total, uint32_t* flags, void* stream);
 int mi_dirichlet_workspace_bytes(int64_t K, int64_t N, int64_t C, size_t* bytes);
 
+/* Largest number of components C of a Normal mixture the site kernel below takes (larger:
+ * MI_EUNSUPPORTED, checked before any device work). */
+#define MI_MIXTURE_MAX_C 1024
+
+/* Normal-mixture site (replaces MixtureSameFamily(Categorical, Normal).log_prob,
+ * mixture_same_family.py:169-179, and its autograd): logits[k, i, c], loc[k, i, c] and
+ * component_scale[k, i, c] each by its own three strides, any of which may be 0 (a particle-
+ * constant tensor, components shared by the rows), value[k, i] by two, optional mask[i]. Per
+ * row, with m = log_softmax(logits) taken here (raw and normalised logits both do) and
+ * z_c = (x - loc_c) / scale_c:
+ *   t_c = m_c - log scale_c - 1/2 log 2 pi - 1/2 z_c^2,  l = logsumexp_c t_c,  r_c = exp(t_c - l)
+ *   total[k] = scale * sum_i mask_i * l_ki
+ * Both maxima are subtracted before the sums (a value far from every component keeps a finite l);
+ * the rows are accumulated in fp64 in a fixed order (no atomics). When non-NULL, dlogits / dloc /
+ * dscale (row-major contiguous [K, N, C]) and dvalue ([K, N]) are written in every entry, zeros on
+ * masked rows:
+ *   dlogits = g0 * scale * (r_c - exp(m_c))         dloc   = g0 * scale * r_c z_c / scale_c
+ *   dscale  = g0 * scale * r_c (z_c^2 - 1) / scale_c  dvalue = -g0 * scale * sum_c r_c z_c / scale_c
+ * A component of logit -inf has r_c = 0 and zero gradients. flags[0] (zeroed by this call) =
+ * MI_FLAG_PARAM unless every observed scale_c > 0 and the row has a finite logit and no NaN logit,
+ * MI_FLAG_SUPPORT for a NaN value of an observed row. The workspace holds the rows' fp64 log
+ * densities. 1 <= C <= MI_MIXTURE_MAX_C. */
+int mi_mixture_normal_forward(const float* logits, int64_t logits_stride_k,
+                              int64_t logits_stride_i, int64_t logits_stride_c, const float* loc,
+                              int64_t loc_stride_k, int64_t loc_stride_i, int64_t loc_stride_c,
+                              const float* component_scale, int64_t scale_stride_k,
+                              int64_t scale_stride_i, int64_t scale_stride_c, int64_t K, int64_t N,
+                              int64_t C, const float* value, int64_t value_stride_k,
+                              int64_t value_stride_i, const uint8_t* mask, int64_t mask_stride_i,
+                              double scale, float g0, float* dlogits, float* dloc, float* dscale,
+                              float* dvalue, void* workspace, size_t workspace_bytes, float* total,
+                              uint32_t* flags, void* stream);
+int mi_mixture_normal_workspace_bytes(int64_t K, int64_t N, int64_t C, size_t* bytes);
+
 /* MultivariateNormal site (replaces MultivariateNormal.log_prob, multivariate_normal.py:255-262,
  * with _batch_mahalanobis at :80-102; sites such as examples/missing-observations.md:42), float64,
  * row-major contiguous value[b, n], loc[b, n] and lower-triangular scale_tril[b, n, n] (the
@@ -705,6 +739,21 @@ int mi_predictive_sample(int family, const float* a, int64_t a_stride_s, int64_t
 int mi_predictive_categorical(const float* logits, int64_t stride_s, int64_t stride_b,
                               int64_t stride_c, int64_t S, int64_t T, int64_t B, int64_t C,
                               uint64_t seed, uint32_t stream_id, int64_t* out, void* stream);
+
+/* MixtureSameFamily(Categorical(logits[S, B, C]), Normal(loc[S, B, C], scale[S, B, C])) with T
+ * replications per sample: row r = (s * T + t) * B + b as above, logits, loc and scale each read
+ * through its own (stride_s, stride_b, stride_c). The component c is mi_predictive_categorical's
+ * choice for the same seed, stream and logits (sub-stream 0); eps is Box-Muller output r % 4 of the
+ * block of quad r / 4 on sub-stream 1 (counter {r / 4, 0, 0, (stream_id << 8) | 1}):
+ *   out[r] = loc_c + scale_c * eps.
+ * out is float32 [S*T*B]. The caps are mi_predictive_categorical's. */
+int mi_predictive_mixture_normal(const float* logits, int64_t logits_stride_s,
+                                 int64_t logits_stride_b, int64_t logits_stride_c,
+                                 const float* loc, int64_t loc_stride_s, int64_t loc_stride_b,
+                                 int64_t loc_stride_c, const float* scale, int64_t scale_stride_s,
+                                 int64_t scale_stride_b, int64_t scale_stride_c, int64_t S,
+                                 int64_t T, int64_t B, int64_t C, uint64_t seed,
+                                 uint32_t stream_id, float* out, void* stream);
 
 /* Poisson(rate) consumes a variable number of words, so element e reads its own stream of Philox
  * blocks, mi_gamma_rsample's scheme on the free sub-stream 3:

@@ -30,6 +30,7 @@ LINEAR_MAX_P = 64
 LINEAR_VALU = 2
 MVN_MAX_N = 1024   # MI_MVN_MAX_N
 DIRICHLET_MAX_C = 1024   # MI_DIRICHLET_MAX_C
+MIXTURE_MAX_C = 1024   # MI_MIXTURE_MAX_C
 LOWRANK_MAX_R = 128   # MI_LOWRANK_MAX_R
 LOWRANK_MAX_D = 1 << 24   # MI_LOWRANK_MAX_D
 PRED_CATEGORICAL_MAX_C = 1024   # MI_PRED_CATEGORICAL_MAX_C
@@ -257,6 +258,13 @@ _SIGNATURES = {
                                             c_i64, c_i64, c_i64, c_vp, c_i64, ctypes.c_double,
                                             ctypes.c_float, c_vp, c_vp, c_vp, ctypes.c_size_t,
                                             c_vp, c_vp, c_vp]),
+    "mi_mixture_normal_workspace_bytes": (ctypes.c_int, [c_i64, c_i64, c_i64,
+                                                         ctypes.POINTER(ctypes.c_size_t)]),
+    "mi_mixture_normal_forward": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64,
+                                                 c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64,
+                                                 c_i64, c_vp, c_i64, c_i64, c_vp, c_i64,
+                                                 ctypes.c_double, ctypes.c_float, c_vp, c_vp, c_vp,
+                                                 c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp, c_vp]),
     "mi_dirichlet_rsample": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, ctypes.c_uint64,
                                             ctypes.c_uint64, c_vp, ctypes.c_uint32, c_i64, c_vp,
                                             c_vp, c_vp]),
@@ -340,6 +348,10 @@ _SIGNATURES = {
     "mi_predictive_categorical": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,
                                                  c_i64, ctypes.c_uint64, ctypes.c_uint32, c_vp,
                                                  c_vp]),
+    "mi_predictive_mixture_normal": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64,
+                                                    c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64,
+                                                    c_i64, c_i64, ctypes.c_uint64, ctypes.c_uint32,
+                                                    c_vp, c_vp]),
     "mi_predictive_poisson": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, ctypes.c_uint64,
                                              ctypes.c_uint32, c_vp, c_vp]),
     "mi_elementwise_rsample": (ctypes.c_int, [ctypes.c_int, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64,

@@ -20,7 +20,7 @@ INCLUDE = os.path.join(ROOT, "include")
 SOURCES = [os.path.join(CSRC, name)
            for name in ("sites.hip", "guide.hip", "elbo.hip", "linear.hip", "minibatch.hip",
                         "adam.hip", "mvn.hip", "mvn_guide.hip", "lowrank_guide.hip", "lowrank_entropy.hip",
-                        "dirichlet.hip", "predictive.hip", "elementwise_guide.hip", "peer.hip", "jit.cpp")]
+                        "dirichlet.hip", "mixture.hip", "predictive.hip", "elementwise_guide.hip", "peer.hip", "jit.cpp")]
 # every header: a change to any of them rebuilds every object
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + [os.path.join(INCLUDE, "mininf_amd.h")]
 EMBEDDED = {"embedded_header.inc": os.path.join(INCLUDE, "mininf_amd.h"),

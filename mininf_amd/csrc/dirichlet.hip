@@ -7,28 +7,19 @@
 //     dirichlet_grad_one -- the per-component function beta_grad.hpp restates),
 //   * Dirichlet.entropy (dirichlet.py:122-130) and its autograd.
 //
-// Layout of every kernel that walks rows: one (particle, row) per group of W = min(64,
-// next_pow2(C)) lanes, lanes striding over the categories, row sums by __shfl_xor inside the group
-// -- many small rows share a wave, a C = 1024 row is one wave looping 16 times. No atomics (the
+// Layout of every kernel that walks rows: the row groups of row_groups.hpp. No atomics (the
 // validation word's OR aside, whose result does not depend on order): every sum has a fixed order,
 // so results do not depend on the launch.
 #include "beta_grad.hpp"
 #include "gamma_sample.hpp"
 #include "internal.hpp"
+#include "row_groups.hpp"
 
 #include <algorithm>
 
 namespace mi {
 
-constexpr int kDirThreads = 256;
-
-// Sum over the W lanes of a row group (W a power of two <= 64; groups are W-aligned, so the
-// exchange partners stay inside the group). Every lane of the wave must be active.
-template <typename T>
-MI_DEV T group_sum(T v, int W) {
-  for (int offset = W >> 1; offset > 0; offset >>= 1) v += __shfl_xor(v, offset, kWave);
-  return v;
-}
+constexpr int kDirThreads = kRowThreads;
 
 // fp64 trigamma: recurrence up to x >= 10, then the asymptotic (Bernoulli-number) series. NaN
 // unless x > 0 (concentrations are positive; a bad one must not spin the recurrence).
@@ -42,18 +33,6 @@ MI_DEV double trigamma(double x) {
   const double r = 1.0 / (x * x);
   return acc + 1.0 / x + 0.5 * r +
          r / x * (1.0 / 6 - r * (1.0 / 30 - r * (1.0 / 42 - r * (1.0 / 30 - r * (5.0 / 66)))));
-}
-
-// The row a lane works on: wave w of the launch holds rows [w * G, w * G + G), G = 64 / W.
-struct RowLane {
-  int sub;       // lane within the row group: categories sub, sub + W, ...
-  int64_t row;   // row index
-};
-
-MI_DEV RowLane row_lane(int shift) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t wave = (int64_t)blockIdx.x * (kDirThreads / kWave) + (threadIdx.x >> 6);
-  return RowLane{lane & ((1 << shift) - 1), wave * (kWave >> shift) + (lane >> shift)};
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -120,19 +99,6 @@ __global__ __launch_bounds__(kDirThreads) void k_dirichlet(
     }
   }
   publish_flags(flags, fl);
-}
-
-// total[k] = scale * sum_i row_lp[k, i]: one wave per particle, lanes striding over rows, fp64.
-__global__ __launch_bounds__(kDirThreads) void k_dirichlet_finalize(
-    const double* __restrict__ row_lp, int64_t K, int64_t N, double scale,
-    float* __restrict__ total) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t k = (int64_t)blockIdx.x * (kDirThreads / kWave) + (threadIdx.x >> 6);
-  double acc = 0.0;
-  if (k < K)
-    for (int64_t i = lane; i < N; i += kWave) acc += row_lp[k * N + i];
-  acc = wave_sum(acc);
-  if (k < K && lane == 0) total[k] = (float)(acc * scale);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -318,28 +284,6 @@ __global__ __launch_bounds__(kDirThreads) void k_dirichlet_entropy(
 
 namespace {
 
-// Lanes per row: min(64, next_pow2(C)), and its log2.
-void row_group(int64_t C, int* W, int* shift) {
-  int w = 1, s = 0;
-  while (w < 64 && w < C) {
-    w <<= 1;
-    ++s;
-  }
-  *W = w;
-  *shift = s;
-}
-
-// Blocks of a row-walking launch over `rows` rows (0: more than a grid holds).
-int64_t row_blocks(int64_t rows, int W) {
-  const int64_t waves = ceil_div(rows, 64 / W);
-  const int64_t blocks = ceil_div(waves, mi::kDirThreads / 64);
-  return blocks <= kMaxGrid ? blocks : 0;
-}
-
-bool shape_ok(int64_t K, int64_t N, int64_t C) {
-  return K >= 1 && N >= 1 && C >= 1 && K <= (INT64_MAX / 8) / N && K * N <= (INT64_MAX / 8) / C;
-}
-
 size_t align8(size_t n) { return (n + 7) & ~(size_t)7; }
 
 }  // namespace
@@ -347,7 +291,7 @@ size_t align8(size_t n) { return (n + 7) & ~(size_t)7; }
 extern "C" {
 
 int mi_dirichlet_workspace_bytes(int64_t K, int64_t N, int64_t C, size_t* bytes) {
-  if (!shape_ok(K, N, C) || bytes == nullptr) return MI_EINVAL;
+  if (!row_shape_ok(K, N, C) || bytes == nullptr) return MI_EINVAL;
   if (C > MI_DIRICHLET_MAX_C) return MI_EUNSUPPORTED;
   *bytes = (size_t)K * (size_t)N * sizeof(double);
   return 0;
@@ -360,7 +304,7 @@ int mi_dirichlet_forward(const float* concentration, int64_t stride_k, int64_t s
                          float* dconcentration, float* dvalue, void* workspace,
                          size_t workspace_bytes, float* total, uint32_t* flags, void* stream) {
   if (concentration == nullptr || value == nullptr || total == nullptr || flags == nullptr ||
-      !shape_ok(K, N, C))
+      !row_shape_ok(K, N, C))
     return MI_EINVAL;
   if (C > MI_DIRICHLET_MAX_C) return MI_EUNSUPPORTED;
   size_t need = 0;
@@ -380,7 +324,7 @@ int mi_dirichlet_forward(const float* concentration, int64_t stride_k, int64_t s
                      dconcentration, dvalue, row_lp, flags, W, shift);
   e = hipGetLastError();
   if (e != hipSuccess) return to_code(e);
-  hipLaunchKernelGGL(mi::k_dirichlet_finalize,
+  hipLaunchKernelGGL(mi::k_rows_finalize,
                      dim3((unsigned)ceil_div(K, mi::kDirThreads / 64)), dim3(mi::kDirThreads), 0,
                      s, row_lp, K, N, scale, total);
   return to_code(hipGetLastError());
@@ -390,7 +334,7 @@ int mi_dirichlet_rsample(const float* concentration, int64_t K, int64_t N, int64
                          uint64_t seed, uint64_t step, const uint64_t* step_device,
                          uint32_t stream_id, int64_t particle_offset, const float* g_in, float* x,
                          void* stream) {
-  if (concentration == nullptr || x == nullptr || !shape_ok(K, N, C) || stream_id > 0xFFFFFFu)
+  if (concentration == nullptr || x == nullptr || !row_shape_ok(K, N, C) || stream_id > 0xFFFFFFu)
     return MI_EINVAL;
   if (C > MI_DIRICHLET_MAX_C) return MI_EUNSUPPORTED;
   int W, shift;
@@ -405,7 +349,7 @@ int mi_dirichlet_rsample(const float* concentration, int64_t K, int64_t N, int64
 
 int mi_dirichlet_rsample_backward_workspace_bytes(int64_t K, int64_t N, int64_t C,
                                                   size_t* bytes) {
-  if (!shape_ok(K, N, C) || bytes == nullptr) return MI_EINVAL;
+  if (!row_shape_ok(K, N, C) || bytes == nullptr) return MI_EINVAL;
   if (C > MI_DIRICHLET_MAX_C) return MI_EUNSUPPORTED;
   const BwdGeometry geo = bwd_geometry(K, N * C, mi::kDirThreads);
   // dot [K, N] and psi_tot [N] (fp64), tot [N] (fp32), then the slices' partial sums
@@ -420,7 +364,7 @@ int mi_dirichlet_rsample_backward(const float* dx, int64_t dx_stride_k, int64_t 
                                   int64_t K, int64_t N, int64_t C, void* workspace,
                                   size_t workspace_bytes, float* dconcentration, void* stream) {
   if (dx == nullptr || x == nullptr || concentration == nullptr || dconcentration == nullptr ||
-      !shape_ok(K, N, C))
+      !row_shape_ok(K, N, C))
     return MI_EINVAL;
   if (C > MI_DIRICHLET_MAX_C) return MI_EUNSUPPORTED;
   size_t need = 0;
@@ -457,7 +401,7 @@ int mi_dirichlet_rsample_backward(const float* dx, int64_t dx_stride_k, int64_t 
 
 int mi_dirichlet_entropy(const float* concentration, int64_t N, int64_t C, float* entropy,
                          float* dconcentration, void* stream) {
-  if (concentration == nullptr || entropy == nullptr || !shape_ok(1, N, C)) return MI_EINVAL;
+  if (concentration == nullptr || entropy == nullptr || !row_shape_ok(1, N, C)) return MI_EINVAL;
   if (C > MI_DIRICHLET_MAX_C) return MI_EUNSUPPORTED;
   int W, shift;
   row_group(C, &W, &shift);

@@ -2,8 +2,9 @@
 //
 // Replaces `distribution.sample(sample_shape)` (reference core.py:192-204, SampleTracer.sample) for
 // the sites broadcast_samples has to simulate: Bernoulli, Exponential, Laplace, Cauchy, HalfCauchy,
-// HalfNormal, LogNormal (mi_predictive_sample), Categorical (mi_predictive_categorical) and Poisson
-// (mi_predictive_poisson), on the counter-based Philox generator of the guide draws.
+// HalfNormal, LogNormal (mi_predictive_sample), Categorical (mi_predictive_categorical), the
+// marginalised Normal mixture (mi_predictive_mixture_normal) and Poisson (mi_predictive_poisson), on
+// the counter-based Philox generator of the guide draws.
 //
 // Layout: the logical space is [S, M] (S samples, M elements per sample), flat element
 // e = s * M + j, the layout mi_normal_rsample has with K = 1 and N = S * M. A parameter is a pointer
@@ -91,9 +92,38 @@ MI_DEV const float* categorical_row(const float* logits, int64_t ss, int64_t sb,
   return logits + s * ss + b * sb;
 }
 
+// What becomes of row r's category c: the category itself ...
+struct EmitCategory {
+  int64_t* out;
+  MI_DEV void operator()(int64_t r, int c) const { out[r] = c; }
+};
+
+// ... or the draw of that component of a Normal mixture: loc_c + scale_c * eps, eps the Box-Muller
+// output r % 4 of the block of quad r / 4 on sub-stream 1 (the category's uniform is sub-stream 0).
+struct EmitMixtureNormal {
+  const float* loc;
+  int64_t ms, mb, mc;
+  const float* scale;
+  int64_t ss, sb, sc;
+  int64_t T, B;
+  uint64_t seed;
+  uint32_t stream_id;
+  float* out;
+  MI_DEV void operator()(int64_t r, int c) const {
+    const U4 w = guide_bits(seed, 0, stream_id, 1, (uint64_t)(r >> 2), 0);
+    float n0, n1;
+    if ((r & 2) == 0) box_muller(w.x, w.y, n0, n1);
+    else box_muller(w.z, w.w, n0, n1);
+    const float eps = (r & 1) == 0 ? n0 : n1;
+    out[r] = categorical_row(loc, ms, mb, T, B, r)[c * mc] +
+             categorical_row(scale, ss, sb, T, B, r)[c * sc] * eps;
+  }
+};
+
+template <typename Emit>
 __global__ __launch_bounds__(kPredThreads) void k_categorical_thread(
     const float* __restrict__ logits, int64_t ss, int64_t sb, int64_t sc, int64_t T, int64_t B,
-    int C, int64_t rows, uint64_t seed, uint32_t stream_id, int64_t* __restrict__ out) {
+    int C, int64_t rows, uint64_t seed, uint32_t stream_id, const Emit emit) {
   const int64_t r = (int64_t)blockIdx.x * kPredThreads + threadIdx.x;
   if (r >= rows) return;
   const float* row = categorical_row(logits, ss, sb, T, B, r);
@@ -111,12 +141,13 @@ __global__ __launch_bounds__(kPredThreads) void k_categorical_thread(
     if (found < 0 && cum > threshold) found = c;
     if (finite_f(l)) last = c;
   }
-  out[r] = found >= 0 ? found : (last >= 0 ? last : C - 1);
+  emit(r, found >= 0 ? found : (last >= 0 ? last : C - 1));
 }
 
+template <typename Emit>
 __global__ __launch_bounds__(kPredThreads) void k_categorical_wave(
     const float* __restrict__ logits, int64_t ss, int64_t sb, int64_t sc, int64_t T, int64_t B,
-    int C, int64_t rows, uint64_t seed, uint32_t stream_id, int64_t* __restrict__ out) {
+    int C, int64_t rows, uint64_t seed, uint32_t stream_id, const Emit emit) {
   constexpr int kWaves = kPredThreads / kWave;
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t first = (int64_t)blockIdx.x * kWaves + threadIdx.x / kWave;
@@ -160,7 +191,7 @@ __global__ __launch_bounds__(kPredThreads) void k_categorical_wave(
 #pragma unroll
     for (int offset = 32; offset > 0; offset >>= 1)
       found = min(found, __shfl_xor(found, offset, kWave));
-    if (lane == 0) out[r] = found < C ? found : (last >= 0 ? last : C - 1);
+    if (lane == 0) emit(r, found < C ? found : (last >= 0 ? last : C - 1));
   }
 }
 
@@ -242,6 +273,34 @@ int64_t bounded_product(int64_t S, int64_t M, int64_t cap) {
   return n <= cap ? n : -1;
 }
 
+// The category of each of the S * T * B rows, handed to `emit` (the argument checks and the two
+// kernels of mi_predictive_categorical).
+template <typename Emit>
+int launch_categorical(const float* logits, int64_t stride_s, int64_t stride_b, int64_t stride_c,
+                       int64_t S, int64_t T, int64_t B, int64_t C, uint64_t seed,
+                       uint32_t stream_id, const Emit& emit, void* stream) {
+  if (logits == nullptr || S < 1 || T < 1 || B < 1 || C < 1 || stream_id > 0xFFFFFFu)
+    return MI_EINVAL;
+  if (C > MI_PRED_CATEGORICAL_MAX_C) return MI_EUNSUPPORTED;
+  const int64_t ST = bounded_product(S, T, kMaxQuadElements);
+  const int64_t rows = ST < 0 ? -1 : bounded_product(ST, B, kMaxQuadElements);
+  if (rows < 0) return MI_EUNSUPPORTED;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (C <= mi::kCategoricalThreadC) {
+    hipLaunchKernelGGL(mi::k_categorical_thread<Emit>,
+                       dim3((unsigned)ceil_div(rows, (int64_t)mi::kPredThreads)),
+                       dim3(mi::kPredThreads), 0, s, logits, stride_s, stride_b, stride_c, T, B,
+                       (int)C, rows, seed, stream_id, emit);
+  } else {
+    // one wave per row, the waves striding over the rows when there are more than the grid holds
+    const int64_t blocks = std::min<int64_t>(ceil_div(rows, mi::kPredThreads / mi::kWave), 1 << 20);
+    hipLaunchKernelGGL(mi::k_categorical_wave<Emit>, dim3((unsigned)blocks),
+                       dim3(mi::kPredThreads), 0, s, logits, stride_s, stride_b, stride_c, T, B,
+                       (int)C, rows, seed, stream_id, emit);
+  }
+  return to_code(hipGetLastError());
+}
+
 }  // namespace
 
 extern "C" {
@@ -292,27 +351,25 @@ int mi_predictive_sample(int family, const float* a, int64_t a_stride_s, int64_t
 int mi_predictive_categorical(const float* logits, int64_t stride_s, int64_t stride_b,
                               int64_t stride_c, int64_t S, int64_t T, int64_t B, int64_t C,
                               uint64_t seed, uint32_t stream_id, int64_t* out, void* stream) {
-  if (logits == nullptr || out == nullptr || S < 1 || T < 1 || B < 1 || C < 1 ||
-      stream_id > 0xFFFFFFu)
-    return MI_EINVAL;
-  if (C > MI_PRED_CATEGORICAL_MAX_C) return MI_EUNSUPPORTED;
-  const int64_t ST = bounded_product(S, T, kMaxQuadElements);
-  const int64_t rows = ST < 0 ? -1 : bounded_product(ST, B, kMaxQuadElements);
-  if (rows < 0) return MI_EUNSUPPORTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (C <= mi::kCategoricalThreadC) {
-    hipLaunchKernelGGL(mi::k_categorical_thread,
-                       dim3((unsigned)ceil_div(rows, (int64_t)mi::kPredThreads)),
-                       dim3(mi::kPredThreads), 0, s, logits, stride_s, stride_b, stride_c, T, B,
-                       (int)C, rows, seed, stream_id, out);
-  } else {
-    // one wave per row, the waves striding over the rows when there are more than the grid holds
-    const int64_t blocks = std::min<int64_t>(ceil_div(rows, mi::kPredThreads / mi::kWave), 1 << 20);
-    hipLaunchKernelGGL(mi::k_categorical_wave, dim3((unsigned)blocks), dim3(mi::kPredThreads), 0,
-                       s, logits, stride_s, stride_b, stride_c, T, B, (int)C, rows, seed, stream_id,
-                       out);
-  }
-  return to_code(hipGetLastError());
+  if (out == nullptr) return MI_EINVAL;
+  return launch_categorical(logits, stride_s, stride_b, stride_c, S, T, B, C, seed, stream_id,
+                            mi::EmitCategory{out}, stream);
+}
+
+int mi_predictive_mixture_normal(const float* logits, int64_t logits_stride_s,
+                                 int64_t logits_stride_b, int64_t logits_stride_c,
+                                 const float* loc, int64_t loc_stride_s, int64_t loc_stride_b,
+                                 int64_t loc_stride_c, const float* scale, int64_t scale_stride_s,
+                                 int64_t scale_stride_b, int64_t scale_stride_c, int64_t S,
+                                 int64_t T, int64_t B, int64_t C, uint64_t seed,
+                                 uint32_t stream_id, float* out, void* stream) {
+  if (loc == nullptr || scale == nullptr || out == nullptr) return MI_EINVAL;
+  const mi::EmitMixtureNormal emit{loc,  loc_stride_s, loc_stride_b, loc_stride_c,
+                                   scale, scale_stride_s, scale_stride_b, scale_stride_c,
+                                   T,    B,            seed,         stream_id,
+                                   out};
+  return launch_categorical(logits, logits_stride_s, logits_stride_b, logits_stride_c, S, T, B, C,
+                            seed, stream_id, emit, stream);
 }
 
 int mi_predictive_poisson(const float* rate, int64_t stride_s, int64_t stride_j, int64_t S,

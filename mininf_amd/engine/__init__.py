@@ -39,8 +39,8 @@ from ..particles import ParticleTrace, SiteRecord
 from ._operands import (FAMILY_CODES, _INTEGER_VALUED, _ONE_PARAMETER, _Operand, _View, _collapse,
                         _float, _to_device)
 from ._groups import _QUERY_ADDRESS, _GroupLauncher, _SiteGroupFn
-from ._rows import (_CategoricalFn, _DirichletFn, _run_categorical, _run_dirichlet,
-                    _run_row_site)
+from ._rows import (_CategoricalFn, _DirichletFn, _MixtureNormalFn, _run_categorical,
+                    _run_dirichlet, _run_mixture_normal, _run_row_site, row_site_fn)
 from ._linear import _LinearLauncher, _LinearSiteFn
 from ._held import (PendingGrad, _FUSED_ADAM_MAX_NUMEL, _PendingStep, _defer_step,
                     attach_optimizer, discard_pending_step, flush_pending_step, grad_meta,
@@ -63,10 +63,9 @@ def log_joint(trace: ParticleTrace, g0: float, device: torch.device) -> LogJoint
     launchers, categorical = plan_groups(trace, g0, device)
     totals: List[torch.Tensor] = []
     pending: List[Tuple[str, dict, List[SiteRecord]]] = []
-    for site, lg, val, mask in categorical:
+    for site, params, val, mask in categorical:
         holder: dict = {}
-        fn = _DirichletFn if site.family == "dirichlet" else _CategoricalFn
-        totals.append(fn.apply(site, holder, g0, lg, val, mask))
+        totals.append(row_site_fn(site).apply(site, holder, g0, *params, val, mask))
         pending.append((site.family, holder, [site]))
     for linear in linears:
         holder = {}
@@ -111,7 +110,7 @@ def _materialize_draws(trace: ParticleTrace, draws) -> None:
 def _lazy_uses(trace: ParticleTrace) -> Tuple[set, set]:
     """
     (all lazy draws in the trace's site tensors, those used where the kernels cannot compute
-    them: linear / categorical / Dirichlet sites, or broadcast beyond the draw's own shape).
+    them: linear / categorical / Dirichlet / mixture sites, or broadcast beyond the draw's own shape).
     """
     seen, bad = set(), set()
     for site in trace.sites:
@@ -120,7 +119,8 @@ def _lazy_uses(trace: ParticleTrace) -> Tuple[set, set]:
             if lazy is None:
                 continue
             seen.add(lazy)
-            if site.linear_X is not None or site.family in ("categorical", "dirichlet") or \
+            if site.linear_X is not None or \
+                    site.family in ("categorical", "dirichlet", "mixture_normal") or \
                     tuple(t.shape[1:]) != tuple(site.site_shape) or \
                     int(site.site_shape.numel()) != lazy.N:
                 bad.add(lazy)

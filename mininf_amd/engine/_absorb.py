@@ -170,8 +170,8 @@ def _absorb_factor(factor: EntropyFactor, samples: Dict[str, torch.Tensor], laun
                 uses.append((which, j, -1))
             else:
                 return None
-    for _, param, value, _ in categorical:   # (logits | concentration, value)
-        for t in (param, value):
+    for _, params, value, _ in categorical:   # (the row site's parameters, value)
+        for t in (*params, value):
             if shares(t):
                 return None
             others.append(t)

@@ -45,8 +45,8 @@ def _elbo_workspace(device: torch.device, nbytes: int) -> torch.Tensor:
 class _ElboPlan:
     """
     Everything one ELBO evaluation launches, in the order of the autograd inputs:
-    site groups (their operand tensors), categorical / Dirichlet sites (logits | concentration,
-    value, mask), linear sites
+    site groups (their operand tensors), categorical / Dirichlet / mixture sites (logits |
+    concentration | logits, loc, scale; value, mask), linear sites
     (theta, sigma), torch-evaluated sites (their [K] log densities) and the entropy factors (their
     parameter tensor, or -- absorbed -- the unconstrained parameters of both parameters).
     """
@@ -94,8 +94,8 @@ class _ElboPlan:
         out: List[Optional[torch.Tensor]] = []
         for li, launcher in enumerate(self.launchers):
             out.extend(launcher.inputs(self.skip_ops.get(li, ())))
-        for _, lg, val, mask in self.categorical:
-            out.extend([lg, val, mask])
+        for _, params, val, mask in self.categorical:
+            out.extend([*params, val, mask])
         for j, linear in enumerate(self.linears):
             theta, sigma = linear.inputs()
             out.append(None if ("lin_theta", j) in self.skip_lin else theta)
@@ -269,14 +269,14 @@ class _ElboPlan:
                         buffers.append(slot_grad[:launcher.num_slots])
             results.append((grads, slot_grad, launcher.workspace))
         cat_results = []
-        for j, ((site, lg, val, mask), holder) in enumerate(zip(self.categorical,
-                                                                 self.cat_holders)):
-            total, dparam, dvalue, flags = _run_row_site(site, self.g0, lg, val, mask,
-                                                         self.flags[j:j + 1])
+        for j, ((site, params, val, mask), holder) in enumerate(zip(self.categorical,
+                                                                    self.cat_holders)):
+            total, dparams, dvalue, flags = _run_row_site(site, self.g0, params, val, mask,
+                                                          self.flags[j:j + 1])
             holder["flags"] = flags
             terms.append(total)
-            buffers.extend(g for g in (dparam, dvalue) if g is not None)
-            cat_results.append((dparam, dvalue))
+            buffers.extend(g for g in (*dparams, dvalue) if g is not None)
+            cat_results.append((dparams, dvalue))
         lin_results = []
         base = len(self.categorical)
         for j, (linear, holder) in enumerate(zip(self.linears, self.lin_holders)):
@@ -547,8 +547,8 @@ class _ElboPlan:
                     out.append(slot_grad[op.slot].reshape(launcher.K, 1))
                 else:
                     out.append(None)
-        for dparam, dvalue in cat_results:
-            out.extend([dparam, dvalue, None])
+        for dparams, dvalue in cat_results:
+            out.extend([*dparams, dvalue, None])
         for j, (linear, dslots) in enumerate(zip(self.linears, lin_results)):
             dtheta, dsigma = linear.grads(dslots)
             out.append(None if ("lin_theta", j) in self.skip_lin else dtheta)

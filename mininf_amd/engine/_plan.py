@@ -125,8 +125,8 @@ def release_unsafe_claims(linears: List["_LinearLauncher"], launchers: List["_Gr
         for op in launcher.operands:
             if op.view.tensor is not None:
                 read.add(_storage(op.view.tensor))
-    for site, lg, val, _ in categorical:
-        read.update(_storage(t) for t in (lg, val) if isinstance(t, torch.Tensor))
+    for site, params, val, _ in categorical:
+        read.update(_storage(t) for t in (*params, val) if isinstance(t, torch.Tensor))
     for key in read & set(drawn):
         linear = drawn[key]
         linear.draw.launch()
@@ -276,8 +276,9 @@ class LogJoint:
 
 def plan_groups(trace: ParticleTrace, g0: float, device: torch.device):
     """
-    Prepare every recorded site for launch: categorical and Dirichlet sites as (site, logits or
-    concentration, value, mask) and the other families packed into site groups sharing their element space and a dense operand.
+    Prepare every recorded site for launch: categorical, Dirichlet and mixture sites as (site,
+    parameters, value, mask) with the parameters a tuple of [K, N, C] tensors (logits |
+    concentration | logits, loc, scale) and the other families packed into site groups sharing their element space and a dense operand.
     """
     K = trace.K
     groups: List[Tuple[torch.Size, _GroupLauncher]] = []
@@ -301,7 +302,7 @@ def plan_groups(trace: ParticleTrace, g0: float, device: torch.device):
             val = _collapse(value.to(torch.int64), K, shape).tensor.expand(K, N)
             mask = None if site.mask is None else site.mask.to(device).bool().expand(shape) \
                 .reshape(1, N).expand(K, N)
-            categorical.append((site, lg, val, mask))
+            categorical.append((site, (lg,), val, mask))
             continue
         if site.family == "dirichlet":
             # planned like a categorical site: (site, concentration, value, mask) as [K, N, C]
@@ -317,7 +318,25 @@ def plan_groups(trace: ParticleTrace, g0: float, device: torch.device):
                 return t.expand((K,) + tuple(shape) + (C,)).reshape(K, N, C)
             mask = None if site.mask is None else site.mask.to(device).bool().expand(shape) \
                 .reshape(1, N).expand(K, N)
-            categorical.append((site, rows(conc), rows(value), mask))
+            categorical.append((site, (rows(conc),), rows(value), mask))
+            continue
+        if site.family == "mixture_normal":
+            # (site, (logits, loc, scale), value, mask): the parameters as [K, N, C] views read
+            # where they lie (stride 0 along K for a particle-constant tensor, along N for
+            # components the rows share), the value and the mask as [K, N]
+            *params, value = (_to_device(_float(t, site.name), K, device, f"site '{site.name}'",
+                                         False)[0] for t in site.tensors)
+            shape = site.site_shape
+            C = max(int(p.shape[-1]) for p in params[1:])
+            N = int(shape.numel())
+
+            def rows(t: torch.Tensor) -> torch.Tensor:
+                t = t.reshape((K,) + (1,) * (len(shape) + 1 - (t.dim() - 1)) + tuple(t.shape[1:]))
+                return t.expand((K,) + tuple(shape) + (C,)).reshape(K, N, C)
+            val = _collapse(value, K, shape).tensor.expand(K, N)
+            mask = None if site.mask is None else site.mask.to(device).bool().expand(shape) \
+                .reshape(1, N).expand(K, N)
+            categorical.append((site, tuple(rows(p) for p in params), val, mask))
             continue
         shape = site.site_shape
         N = int(shape.numel())

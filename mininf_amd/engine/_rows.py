@@ -1,6 +1,8 @@
 """
-Categorical and Dirichlet sites: one row of C entries per element, launched on their own
-(``mi_categorical_forward`` / ``mi_dirichlet_forward``).
+Categorical, Dirichlet and Normal-mixture sites: one row of C entries per element, launched on
+their own (``mi_categorical_forward`` / ``mi_dirichlet_forward`` / ``mi_mixture_normal_forward``).
+The planner's entry of such a site is (site, parameters, value, mask) with the parameters a tuple
+of [K, N, C] tensors: one for a Categorical or Dirichlet site, three for a mixture.
 """
 from __future__ import annotations
 
@@ -115,12 +117,85 @@ class _DirichletFn(torch.autograd.Function):
         return None, None, None, ctx.grads[0], ctx.grads[1], None
 
 
-def _run_row_site(site: SiteRecord, g0: float, param: torch.Tensor, value: torch.Tensor,
-                  mask: Optional[torch.Tensor], flags: Optional[torch.Tensor] = None):
-    """A categorical or Dirichlet site's launch: (total, dparameter, dvalue, flags)."""
+def _run_mixture_normal(site: SiteRecord, g0: float, params: Tuple[torch.Tensor, ...],
+                        value: torch.Tensor, mask: Optional[torch.Tensor],
+                        need: Tuple[bool, bool, bool, bool],
+                        flags: Optional[torch.Tensor] = None):
+    """
+    Launch ``mi_mixture_normal_forward``: (total [K], speculative (dlogits, dloc, dscale) and
+    dvalue or None, flags [1]). ``params``: logits, loc, scale as [K, N, C] views read through
+    their own strides (0 where a tensor is particle- or row-constant); ``value`` [K, N].
+    ``need``: which of the four gradients to write.
+    """
+    K, N, C = params[0].shape
+    device = params[0].device
+    # contiguous [K, N, C] / [K, N], every entry written
+    dparams = tuple(torch.empty((K, N, C), dtype=torch.float32, device=device) if wanted else None
+                    for wanted in need[:3])
+    dvalue = torch.empty((K, N), dtype=torch.float32, device=device) if need[3] else None
+    size = ctypes.c_size_t()
+    lib = nat.lib()
+    nat.check(lib.mi_mixture_normal_workspace_bytes(K, N, C, ctypes.byref(size)),
+              "mi_mixture_normal_workspace_bytes")
+    workspace = torch.empty(max(1, size.value), dtype=torch.uint8, device=device)
+    total = torch.empty(K, dtype=torch.float32, device=device)
+    if flags is None:
+        flags = torch.empty(1, dtype=torch.int32, device=device)
+    strided = [x for t in params for x in (t.data_ptr(), t.stride(0), t.stride(1), t.stride(2))]
+    nat.check(lib.mi_mixture_normal_forward(
+        *strided, K, N, C, value.data_ptr(), value.stride(0), value.stride(1),
+        None if mask is None else mask.data_ptr(), 0 if mask is None else mask.stride(1),
+        site.scale, g0, *[nat.ptr(g) for g in dparams], nat.ptr(dvalue), workspace.data_ptr(),
+        size.value, total.data_ptr(), flags.data_ptr(), nat.stream_handle(device)),
+        "mi_mixture_normal_forward")
+    return total, dparams, dvalue, flags
+
+
+class _MixtureNormalFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, site: SiteRecord, holder: dict, g0: float, logits: torch.Tensor,
+                loc: torch.Tensor, scale: torch.Tensor, value: torch.Tensor,
+                mask: Optional[torch.Tensor]):  # type: ignore[override]
+        total, dparams, dvalue, flags = _run_mixture_normal(
+            site, g0, (logits, loc, scale), value, mask,
+            (logits.requires_grad, loc.requires_grad, scale.requires_grad, value.requires_grad))
+        holder["flags"] = flags
+        ctx.grads = (*dparams, dvalue)
+        ctx.g0 = g0
+        return total
+
+    @staticmethod
+    def backward(ctx, g):  # type: ignore[override]
+        g = g.contiguous()
+        for grad in ctx.grads:
+            if grad is not None:
+                K, M = grad.shape[0], grad[0].numel()
+                nat.check(nat.lib().mi_scale_rows(grad.data_ptr(), M, 1, K, M, g.data_ptr(),
+                                                  ctx.g0, nat.stream_handle(g.device)),
+                          "mi_scale_rows")
+        return (None, None, None, *ctx.grads, None)
+
+
+def _run_row_site(site: SiteRecord, g0: float, params: Tuple[torch.Tensor, ...],
+                  value: torch.Tensor, mask: Optional[torch.Tensor],
+                  flags: Optional[torch.Tensor] = None):
+    """A categorical, Dirichlet or mixture site's launch: (total, the parameters' gradients as a
+    tuple, dvalue, flags)."""
+    if site.family == "mixture_normal":
+        return _run_mixture_normal(site, g0, params, value, mask,
+                                   (*[p.requires_grad for p in params], value.requires_grad),
+                                   flags)
+    param, = params
     if site.family == "dirichlet":
-        return _run_dirichlet(site, g0, param, value, mask,
-                              (param.requires_grad, value.requires_grad), flags)
+        total, dconc, dvalue, flags = _run_dirichlet(
+            site, g0, param, value, mask, (param.requires_grad, value.requires_grad), flags)
+        return total, (dconc,), dvalue, flags
     total, dlogits, flags = _run_categorical(site, g0, param, value, mask, param.requires_grad,
                                              flags)
-    return total, dlogits, None, flags
+    return total, (dlogits,), None, flags
+
+
+def row_site_fn(site: SiteRecord):
+    """The autograd function of a row site evaluated on its own (engine.log_joint)."""
+    return {"dirichlet": _DirichletFn, "mixture_normal": _MixtureNormalFn}.get(site.family,
+                                                                            _CategoricalFn)

@@ -30,7 +30,7 @@ import torch
 from torch.distributions import Bernoulli, Beta, Binomial, Categorical, Cauchy, Dirichlet, \
     Distribution, \
     Exponential, ExpTransform, Gamma, HalfCauchy, HalfNormal, Laplace, LogNormal, \
-    MultivariateNormal, NegativeBinomial, Normal, Poisson, PowerTransform, StudentT, \
+    MixtureSameFamily, MultivariateNormal, NegativeBinomial, Normal, Poisson, PowerTransform, StudentT, \
     TransformedDistribution
 from torch.distributions.constraints import Constraint
 from torch.distributions.utils import lazy_property
@@ -96,7 +96,9 @@ class SiteRecord:
 
     ``roles`` holds output indices into the vmapped function's outputs for the family's roles
     (Normal: loc, scale, value; Bernoulli: logits|probs, value; Beta: concentration1,
-    concentration0, value; Categorical: logits, value; Dirichlet: concentration, value). After :func:`trace_particles` returns,
+    concentration0, value; Categorical: logits, value; Dirichlet: concentration, value;
+    MixtureSameFamily of Normals: mixture logits, component loc, component scale, value). After
+    :func:`trace_particles` returns,
     ``tensors`` holds the corresponding [K, ...] tensors.
     """
     name: str
@@ -316,6 +318,12 @@ def _classify(distribution: Distribution) -> Tuple[str, List[Any], float]:
         return "categorical", [distribution.logits], 0.0
     if cls is Dirichlet and _kernel_dirichlet(distribution):
         return "dirichlet", [distribution.concentration], 0.0
+    if cls is MixtureSameFamily and _kernel_mixture(distribution):
+        # the mixture weights through .logits, as the Categorical site: for a `probs` construction
+        # that is torch's own lazy probs_to_logits, inside the trace
+        component = distribution.component_distribution
+        return "mixture_normal", [distribution.mixture_distribution.logits, component.loc,
+                                  component.scale], 0.0
     if cls is Gamma:
         return "gamma", [distribution.concentration, distribution.rate], 0.0
     if cls is Poisson:
@@ -361,6 +369,19 @@ def _kernel_dirichlet(distribution: Dirichlet) -> bool:
     concentration = distribution.concentration
     return isinstance(concentration, torch.Tensor) and concentration.dtype == torch.float32 and \
         1 <= int(concentration.shape[-1]) <= _native.DIRICHLET_MAX_C
+
+
+def _kernel_mixture(distribution: MixtureSameFamily) -> bool:
+    """A mixture the site kernel takes (mi_mixture_normal_forward): Categorical weights over scalar
+    Normal components (the last batch axis of loc / scale is the component axis), float32 tensors,
+    at most MI_MIXTURE_MAX_C components. Any other keeps the torch path."""
+    mixture, component = distribution.mixture_distribution, distribution.component_distribution
+    if type(mixture) is not Categorical or type(component) is not Normal:
+        return False
+    tensors = (mixture._param, component.loc, component.scale)
+    return all(isinstance(t, torch.Tensor) and t.dtype == torch.float32 for t in tensors) and \
+        len(component.batch_shape) >= 1 and \
+        1 <= int(component.batch_shape[-1]) <= _native.MIXTURE_MAX_C
 
 
 def _is_log_normal(distribution: Distribution) -> bool:
@@ -514,12 +535,19 @@ class ParticleTracer(TracerMixin):
         if family == "dirichlet" and (data.dtype != torch.float32 or data.dim() < 1 or
                                       data.shape[-1] != distribution.event_shape[0]):
             family, params = "torch", []   # the kernel reads float32 rows of C categories
+        if family == "mixture_normal" and data.dtype != torch.float32:
+            family, params = "torch", []   # the kernel reads float32 values
         if family == "categorical":
             shape = broadcast_shapes(tuple(data.shape), tuple(distribution.batch_shape))
         elif family == "dirichlet":
             shape = broadcast_shapes(tuple(data.shape[:-1]), tuple(distribution.batch_shape))
             if mask is not None:
                 mask = mask.all(-1)   # a row is observed when all its categories are
+        elif family == "mixture_normal":
+            mixture = cast(MixtureSameFamily, distribution)
+            shape = broadcast_shapes(tuple(data.shape),
+                                     tuple(mixture.mixture_distribution.batch_shape),
+                                     tuple(mixture.component_distribution.batch_shape[:-1]))
         elif family != "torch":
             shape = broadcast_shapes(tuple(data.shape), *[tuple(p.shape) for p in params])
         else:
@@ -550,7 +578,7 @@ class ParticleTracer(TracerMixin):
                 linear = info.root or info
             params = [p if (linear is not None and j == 0) else mode.materialize(p)
                       for j, p in enumerate(params)]
-            if family == "dirichlet":
+            if family in ("dirichlet", "mixture_normal"):
                 data = mode.materialize(data)
 
         # Value support is checked by the site kernels (fused flag); constraint checks on the

@@ -3,7 +3,8 @@ Predictive draws on the HIP samplers: the sites ``broadcast_samples`` (reference
 ``core.py:548-584``) has to simulate -- ``SampleTracer.sample`` draws them with the distribution's
 own ``sample`` (``core.py:192-204``) -- come from the same counter-based Philox generator as the
 guide draws (``mi_normal_rsample`` / ``mi_gamma_rsample`` / ``mi_beta_rsample`` and the predictive
-kernels ``mi_predictive_sample`` / ``mi_predictive_categorical`` / ``mi_predictive_poisson``), so a
+kernels ``mi_predictive_sample`` / ``mi_predictive_categorical`` /
+``mi_predictive_mixture_normal`` / ``mi_predictive_poisson``), so a
 predictive run is reproducible from one seed and independent of how the samples are batched or
 sharded.
 
@@ -17,8 +18,9 @@ S' samples alone; a shard that starts at a later sample has its own numbering fr
 
 Drawn natively (exact type, float32 device parameters): Normal, Gamma, Beta, Bernoulli (probs or
 logits, whichever the instance holds), Exponential, Laplace, Cauchy, HalfCauchy, HalfNormal,
-LogNormal, Poisson and Categorical (up to 1024 categories). Everything else keeps torch's
-``sample`` and torch's generator.
+LogNormal, Poisson, Categorical (up to 1024 categories) and MixtureSameFamily of a Categorical
+over scalar Normal components (up to 1024 components). Everything else keeps torch's ``sample``
+and torch's generator.
 """
 from __future__ import annotations
 
@@ -28,14 +30,14 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 from torch.distributions import (Bernoulli, Beta, Categorical, Cauchy, Distribution, Exponential,
-                                 Gamma, HalfCauchy, HalfNormal, Laplace, LogNormal, Normal,
-                                 Poisson)
+                                 Gamma, HalfCauchy, HalfNormal, Laplace, LogNormal,
+                                 MixtureSameFamily, Normal, Poisson)
 from torch.masked import MaskedTensor
 
 from . import _native as nat
 
 NORMAL, GAMMA, BETA = 0, 1, 2
-POISSON, CATEGORICAL = 3, 4
+POISSON, CATEGORICAL, MIXTURE_NORMAL = 3, 4, 5
 # families of mi_predictive_sample: SAMPLE + its MI_PRED_* code
 SAMPLE = 16
 # stream ids of predictive draws: apart from the guide factors' (their factor index)
@@ -92,6 +94,12 @@ def _params(distribution: Distribution) -> Optional[Tuple[int, Sequence[torch.Te
     if cls is Categorical:
         held = distribution.__dict__
         return CATEGORICAL, (held["logits"] if "logits" in held else held["probs"],)
+    if cls is MixtureSameFamily and type(distribution.mixture_distribution) is Categorical and \
+            type(distribution.component_distribution) is Normal:
+        held = distribution.mixture_distribution.__dict__
+        component = distribution.component_distribution
+        return MIXTURE_NORMAL, (held["logits"] if "logits" in held else held["probs"],
+                                component.loc, component.scale)
     return None
 
 
@@ -103,6 +111,10 @@ def supported(distribution: Distribution) -> bool:
         return False
     family, params = found
     if family == CATEGORICAL and not 1 <= params[0].shape[-1] <= nat.PRED_CATEGORICAL_MAX_C:
+        return False
+    if family == MIXTURE_NORMAL and not (
+            isinstance(params[1], torch.Tensor) and params[1].dim() >= 1 and
+            1 <= params[1].shape[-1] <= nat.PRED_CATEGORICAL_MAX_C):
         return False
     return all(isinstance(t, torch.Tensor) and not isinstance(t, MaskedTensor) and
                t.dtype == torch.float32 and _resident(t) for t in params)
@@ -266,6 +278,61 @@ class _CategoricalFn(torch.autograd.Function):
         return _categorical_batched(phys, shape, seed, stream_id), 0
 
 
+def _component_rows(t: torch.Tensor, S: int, B: int, C: int) -> Tuple[torch.Tensor, Tuple]:
+    """A physical ``[S, *batch, C]`` parameter as [S, B, C] rows (a view where one exists) and the
+    strides to read them through (0 along an axis of one entry or one shared by its entries)."""
+    try:
+        rows = t.view(S, B, C)
+    except RuntimeError:
+        rows = t.reshape(S, B, C)
+    ss, sb, sc = rows.stride()
+    return rows, (0 if S == 1 else ss, 0 if B == 1 else sb, 0 if C == 1 else sc)
+
+
+def _mixture_batched(phys: Sequence[torch.Tensor], shape: Tuple[int, ...], seed: int,
+                     stream_id: int) -> torch.Tensor:
+    """Normal-mixture draws for physical logits / loc / scale ``[S, *batch_j, C]`` (each batch_j
+    broadcastable to the site's batch shape): ``[S, *shape, *batch]`` float32."""
+    S, C = phys[0].shape[0], max(t.shape[-1] for t in phys)
+    batch = tuple(torch.broadcast_shapes(*[tuple(t.shape[1:-1]) for t in phys]))
+    B, T = max(1, math.prod(batch)), max(1, math.prod(shape))
+    args: List = []
+    keep = []
+    for t in phys:
+        t = t.reshape(S, *([1] * (len(batch) - (t.dim() - 2))), *t.shape[1:])
+        rows, strides = _component_rows(t.expand(S, *batch, C), S, B, C)
+        keep.append(rows)
+        args.extend((rows.data_ptr(), *strides))
+    device = phys[0].device
+    out = torch.empty(S * T * B, dtype=torch.float32, device=device)
+    nat.check(nat.lib().mi_predictive_mixture_normal(
+        *args, S, T, B, C, seed & 0xFFFFFFFFFFFFFFFF, stream_id, out.data_ptr(),
+        nat.stream_handle(device)), "mi_predictive_mixture_normal")
+    return out.reshape((S,) + tuple(shape) + batch)
+
+
+class _MixtureFn(torch.autograd.Function):
+    """draw(index, logits, loc, scale): as _CategoricalFn, for three parameters whose trailing
+    axis is the component axis."""
+    @staticmethod
+    def forward(index, logits, loc, scale, shape, seed, stream_id):  # type: ignore[override]
+        phys = [t.unsqueeze(0) for t in (logits, loc, scale)]
+        return _mixture_batched(phys, shape, seed, stream_id).squeeze(0)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):  # type: ignore[override]
+        ctx.mark_non_differentiable(output)
+
+    @staticmethod
+    def vmap(info, in_dims, index, logits, loc, scale, shape, seed,
+             stream_id):  # type: ignore[override]
+        S = info.batch_size
+        phys = [t.expand(S, *t.shape) if d is None else
+                t.movedim(d if d >= 0 else d + t.dim(), 0)
+                for t, d in zip((logits, loc, scale), in_dims[1:4])]
+        return _mixture_batched(phys, shape, seed, stream_id), 0
+
+
 def draw(distribution: Distribution, sample_shape: torch.Size, index: torch.Tensor, seed: int,
          stream_id: int) -> torch.Tensor:
     """``distribution.sample(sample_shape)`` inside the predictive vmap, on the HIP samplers."""
@@ -280,6 +347,12 @@ def draw(distribution: Distribution, sample_shape: torch.Size, index: torch.Tens
                 logits = torch.log(logits)   # probs: zero stays -inf, never drawn
             return _CategoricalFn.apply(index, logits, tuple(sample_shape), seed,
                                         STREAM_BASE + stream_id)
+        if family == MIXTURE_NORMAL:
+            logits = params[0].detach()
+            if "logits" not in distribution.mixture_distribution.__dict__:
+                logits = torch.log(logits)   # probs: zero stays -inf, never drawn
+            return _MixtureFn.apply(index, logits, params[1].detach(), params[2].detach(),
+                                    tuple(sample_shape), seed, STREAM_BASE + stream_id)
         a, b = params[0].detach(), params[-1].detach()
         return _DrawFn.apply(index, a, b, family, tuple(sample_shape), seed,
                              STREAM_BASE + stream_id)
