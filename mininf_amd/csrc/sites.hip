@@ -30,6 +30,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 
 #include "internal.hpp"
 #include "jit.hpp"
@@ -610,7 +611,132 @@ MI_DEV void beta_side_block(const mi_side& S, int64_t b) {
 // chunk: elements per chunk, a multiple of 32 and at most kSmemMaxChunk (the host sizes it so that
 // chunks x particle blocks fill the chip's workgroup slots: make_plan).
 constexpr int kSmemMaxChunk = 4096;
-template <int FAMILY, int kSmemP, bool SUFF = false>
+
+// The matrix loop of k_site_bcast_smem (mode bit 3, MININF_AMD_BCAST_MFMA): a chunk whose elements
+// are all exactly 0 or 1 is summed on the bf16 matrix cores with no rounding anywhere.
+//   * x_i in {0, 1} is exact in bf16.
+//   * a finite fp32 logit is the exact sum of three bf16 pieces, h = bf16(l), m = bf16(l - h),
+//     lo = bf16(l - h - m) (the differences are exact in fp32; pieces below bf16's normal range
+//     lose at most 2^-126 each, and a non-finite logit is carried as (l, 0, 0)).
+//   * every accumulator element is (a count <= 4096) x (one piece): 13 + 8 bits, exact in fp32 in
+//     any order as long as each piece keeps accumulators of its own. The pieces meet in fp64.
+// D = A B with v_mfma_f32_16x16x32_bf16: A[row][k] holds 512 consecutive elements of the staged
+// chunk (any element may sit in any slot: all of D's rows are added up at the end), B[k][col] is
+// the piece of the tile's particle `col` in every k. A wave takes the 4 x 64 particles its lanes
+// own in passes of kMatrixP particles per lane: 4 column tiles x 3 pieces per particle slot, each
+// with a 4-register accumulator and a 4-register B fragment -- 2 x 4 x 3 x (4 + 4) = 192 registers
+// a pass, two waves per SIMD (all four slots in one pass take 384: one wave per SIMD).
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));   // a fragment as its four registers
+constexpr int kMatrixP = 2;
+constexpr int kFragElems = 512;   // elements per A fragment: 16 rows x 32 k
+
+MI_DEV float bf16_round(float v) { return (float)(__bf16)v; }
+
+// The three pieces of a logit, as the bf16 pattern repeated over a B fragment's eight k.
+MI_DEV void logit_pieces(float l, i32x4 (&b)[3]) {
+  float piece[3] = {l, 0.0f, 0.0f};
+  if (__builtin_isfinite(l)) {
+    float h = bf16_round(l);
+    // (rounding to nearest can reach infinity just below FLT_MAX: truncate there instead)
+    if (!__builtin_isfinite(h)) h = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, l) & 0xffff0000u);
+    const float r = l - h;
+    const float m = bf16_round(r);
+    piece[0] = h;
+    piece[1] = m;
+    piece[2] = bf16_round(r - m);
+  }
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    const int v = (int)(__builtin_bit_cast(uint32_t, piece[q]) >> 16);   // (a bf16 value: exact)
+    const int vv = v | (v << 16);
+    b[q] = i32x4{vv, vv, vv, vv};
+  }
+}
+
+// sum_i x_i l_k for the kSmemP particles of every lane, from the chunk staged in `xa` as bf16
+// (zeros past its end, up to a whole fragment). `first_k`: the wave's first particle of slot 0.
+template <int kSmemP>
+MI_DEV void bcast_matrix_loop(const __bf16* xa, int nfrag, const f32x2 (&ld)[kSmemP],
+                              double (&acc)[kSmemP], int64_t first_k, int64_t K) {
+  static_assert(kSmemP % kMatrixP == 0, "whole passes");
+  const int lane = threadIdx.x & 63;
+  const int col = lane & 15, grp = lane >> 4;
+  const i32x4* frag = reinterpret_cast<const i32x4*>(xa) + lane;
+#pragma unroll
+  for (int p0 = 0; p0 < kSmemP; p0 += kMatrixP) {
+    // (wave-uniform: a pass none of whose particles exist is skipped; its lanes store nothing)
+    if (first_k + (int64_t)p0 * kBcastThreads >= K) continue;
+    i32x4 b[kMatrixP][4][3];
+    f32x4 d[kMatrixP][4][3];
+#pragma unroll
+    for (int pp = 0; pp < kMatrixP; ++pp)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        logit_pieces(__shfl(ld[p0 + pp].x, g * 16 + col, 64), b[pp][g]);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) d[pp][g][q] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      }
+    // The loop is written out: from the builtin the compiler routes half the accumulators through
+    // a scratch tile, four register moves and a wait per instruction. Accumulators are tied in
+    // AGPRs, fragments stay in VGPRs; between two instructions on one accumulator stand 23 others.
+    // The compiler's hazard recogniser does not see inside the assembly: after a toolchain change
+    // read the ISA of this loop again (the accumulators' zeroing before the first instruction,
+    // the s_waitcnt before the fragment's first use, the waits after the loop).
+    int f = 0;
+    i32x4 next = frag[0];
+    do {   // (nfrag >= 1: a chunk is never empty. The next fragment's read is issued ahead of
+           // this fragment's 24 instructions and waited for behind them: one iteration of overlap,
+           // not a second buffer.)
+      const i32x4 a = next;
+      next = frag[min(f + 1, nfrag - 1) * (kFragElems / 8)];
+#pragma unroll
+      for (int pp = 0; pp < kMatrixP; ++pp)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+#pragma unroll
+          for (int q = 0; q < 3; ++q)
+            __asm__ volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0"
+                             : "+a"(d[pp][g][q]) : "v"(a), "v"(b[pp][g][q]));
+    } while (++f < nfrag);
+    // v_mfma_f32_16x16x32_bf16 is an 8-pass instruction, and a VALU read of a matrix result
+    // has to stand passes + 3 = 11 wait states behind it (19 behind a 16-pass one; the compiler's
+    // hazard table for gfx950). Each statement below waits 32 (two s_nop 15); there are kMatrixP
+    // of them, in order, each tied to half the accumulators.
+#pragma unroll
+    for (int pp = 0; pp < kMatrixP; ++pp)
+      __asm__ volatile("s_nop 15\n\ts_nop 15"
+                       : "+a"(d[pp][0][0]), "+a"(d[pp][0][1]), "+a"(d[pp][0][2]), "+a"(d[pp][1][0]),
+                         "+a"(d[pp][1][1]), "+a"(d[pp][1][2]), "+a"(d[pp][2][0]), "+a"(d[pp][2][1]),
+                         "+a"(d[pp][2][2]), "+a"(d[pp][3][0]), "+a"(d[pp][3][1]), "+a"(d[pp][3][2]));
+    // D's rows: four registers, then the four lane groups. Lane group g keeps tile g (its lanes
+    // own that tile's particles), so the groups trade halves instead of all summing every tile.
+    // (fp32, exact: count x piece.)
+#pragma unroll
+    for (int pp = 0; pp < kMatrixP; ++pp) {
+      double total = 0.0;
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        float v[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          v[g] = (d[pp][g][q].x + d[pp][g][q].y) + (d[pp][g][q].z + d[pp][g][q].w);
+        const bool hi = grp >= 2, odd = (grp & 1) != 0;
+        const float w0 = (hi ? v[2] : v[0]) + __shfl_xor(hi ? v[0] : v[2], 32, 64);
+        const float w1 = (hi ? v[3] : v[1]) + __shfl_xor(hi ? v[1] : v[3], 32, 64);
+        const float t = (odd ? w1 : w0) + __shfl_xor(odd ? w0 : w1, 16, 64);
+        total += (double)t;
+      }
+      acc[p0 + pp] = total;
+    }
+  }
+}
+
+// MATRIX: the instantiation that holds the matrix loop (236 / 232 registers with 96 AGPRs and 8 KB
+// of LDS: two waves per SIMD). Without it the kernel is the scalar-load loop alone, at its 78
+// registers and four workgroups per CU: what MININF_AMD_BCAST_MFMA=0 launches.
+template <int FAMILY, int kSmemP, bool SUFF = false, bool MATRIX = false>
 __global__ __launch_bounds__(kBcastThreads) void k_site_bcast_smem(const mi_group G,
                                                                    float* __restrict__ part,
                                                                    int64_t nseg, int gy,
@@ -619,12 +745,14 @@ __global__ __launch_bounds__(kBcastThreads) void k_site_bcast_smem(const mi_grou
                                                                    double* __restrict__ ksum) {
   __shared__ float scratch[kBcastThreads / 64];
   __shared__ double dscratch[kBcastThreads / 64];
+  __shared__ __attribute__((aligned(16))) __bf16 xa[MATRIX ? kSmemMaxChunk : 8];   // the matrix loop's chunk
   kernarg_prefetch<(int)sizeof(mi_group)>();
   // mode bit 0: rank-one slot layout; bit 1: progress-balanced wave priority (below); bit 2:
   // particle-summed values
   const int rank1 = mode & 1;
   const bool balance = (mode & 2) != 0;
   const bool ksummed = (mode & 4) != 0;
+  constexpr bool try_matrix = MATRIX && !SUFF;
   const int64_t chunks = nseg - 1;
   const int64_t padded = (chunks + 7) / 8 * 8;
   const int64_t b = blockIdx.x;
@@ -674,6 +802,71 @@ __global__ __launch_bounds__(kBcastThreads) void k_site_bcast_smem(const mi_grou
   double acc[kSmemP];
 #pragma unroll
   for (int p = 0; p < kSmemP; ++p) acc[p] = 0.0;
+
+  // ---- chunk sum and support flags (vector loads) ----------------------------------------------
+  // Each lane takes kSmemMaxChunk / kBcastThreads consecutive elements (those within the chunk)
+  // with all its loads in flight at once (a strided loop waits for one L2 round trip per element
+  // group, at the end of every wave). STAGE: the lane's elements also go to `xa` as bf16, zeros
+  // past the chunk's end.
+  constexpr int kPerLane = kSmemMaxChunk / kBcastThreads;
+  static_assert(kPerLane % 8 == 0, "whole float4 groups, and whole 16-byte bf16 groups, per lane");
+  float s_a = 0.0f;
+  auto chunk_pass = [&](auto stage_tag) {
+    constexpr bool STAGE = decltype(stage_tag)::value && MATRIX;
+    const int e0 = (int)threadIdx.x * kPerLane;
+    const float* xl = xg + i0 + e0;
+    float v[kPerLane];
+    if (e0 + kPerLane <= len && (reinterpret_cast<uintptr_t>(xl) & 15) == 0) {
+#pragma unroll
+      for (int q = 0; q < kPerLane / 4; ++q) {
+        const float4 t = reinterpret_cast<const float4*>(xl)[q];
+        v[4 * q] = t.x;
+        v[4 * q + 1] = t.y;
+        v[4 * q + 2] = t.z;
+        v[4 * q + 3] = t.w;
+      }
+#pragma unroll
+      for (int e = 0; e < kPerLane; ++e) {
+        fl |= !(v[e] == 0.0f || v[e] == 1.0f) ? MI_FLAG_SUPPORT : 0u;
+        s_a += v[e];
+      }
+    } else {
+#pragma unroll 1
+      for (int e = e0; e < len && e < e0 + kPerLane; ++e) {
+        const float t = xg[i0 + e];
+        fl |= !(t == 0.0f || t == 1.0f) ? MI_FLAG_SUPPORT : 0u;
+        s_a += t;
+        if (STAGE) xa[e] = (__bf16)t;
+      }
+      if (STAGE)
+        for (int e = max(e0, len); e < e0 + kPerLane; ++e) xa[e] = (__bf16)0.0f;
+      return;
+    }
+    if (STAGE) {
+#pragma unroll
+      for (int q = 0; q < kPerLane / 8; ++q) {
+        bf16x8 t;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) t[e] = (__bf16)v[8 * q + e];
+        reinterpret_cast<bf16x8*>(xa + e0)[q] = t;
+      }
+    }
+  };
+  // The matrix loop needs the whole chunk to be 0/1, so with it enabled the pass runs first: it
+  // stages the chunk, and the workgroup agrees on the answer (wave-uniform, no host round trip).
+  bool matrix = false;
+  if constexpr (try_matrix) {
+    chunk_pass(std::true_type{});
+    s_a = block_sum(s_a, scratch);
+    matrix = __syncthreads_or((fl & MI_FLAG_SUPPORT) != 0u ? 1 : 0) == 0;
+  }
+  if constexpr (try_matrix)
+    if (matrix)
+      bcast_matrix_loop<kSmemP>(xa, (len + kFragElems - 1) / kFragElems, ld, acc,
+                                kblock * (kBcastThreads * kSmemP) + (threadIdx.x & ~63), K);
+
+  // (a chunk with any other value, and every chunk with the matrix loop off: the scalar-load loop)
+  const int vlen = matrix ? 0 : len;
   smem_float* xs = (smem_float*)(xg + i0);
   auto flush = [&](const f32x2 (&in)[2][kSmemP]) {
 #pragma unroll
@@ -685,7 +878,7 @@ __global__ __launch_bounds__(kBcastThreads) void k_site_bcast_smem(const mi_grou
   // for all of them: one group of lookahead). Even and odd element pairs go to separate
   // accumulators, 2 kSmemP independent chains of 64 terms per block.
   constexpr int kGroup = 32, kBlock = 256;
-  const int nfull = SUFF ? 0 : len & ~(kBlock - 1);
+  const int nfull = SUFF ? 0 : vlen & ~(kBlock - 1);
   int j = 0;
   if (nfull > 0) {
     float xc[kGroup];
@@ -727,15 +920,15 @@ __global__ __launch_bounds__(kBcastThreads) void k_site_bcast_smem(const mi_grou
       flush(in);
     }
   }
-  if (!SUFF && j + kGroup <= len) {   // whole groups of 32 past the last whole block
+  if (!SUFF && j + kGroup <= vlen) {   // whole groups of 32 past the last whole block
     f32x2 in[2][kSmemP];
 #pragma unroll
     for (int p = 0; p < kSmemP; ++p) in[0][p] = in[1][p] = f32x2{0.0f, 0.0f};
     float xc[kGroup];
 #pragma unroll
     for (int e = 0; e < kGroup; ++e) xc[e] = xs[j + e];
-    for (; j + kGroup <= len; j += kGroup) {
-      const int nxt = min(j + kGroup, len - kGroup);   // in bounds; the last is unused
+    for (; j + kGroup <= vlen; j += kGroup) {
+      const int nxt = min(j + kGroup, vlen - kGroup);   // in bounds; the last is unused
       float xn[kGroup];
 #pragma unroll
       for (int e = 0; e < kGroup; ++e) xn[e] = xs[nxt + e];
@@ -751,12 +944,12 @@ __global__ __launch_bounds__(kBcastThreads) void k_site_bcast_smem(const mi_grou
     }
     flush(in);
   }
-  if (!SUFF && j < len) {   // the chunk's tail: element pairs, a zero for an odd last element
+  if (!SUFF && j < vlen) {   // the chunk's tail: element pairs, a zero for an odd last element
     f32x2 in[2][kSmemP];
 #pragma unroll
     for (int p = 0; p < kSmemP; ++p) in[0][p] = in[1][p] = f32x2{0.0f, 0.0f};
-    for (int e = 0; j < len; j += 2, ++e) {
-      const f32x2 xv = f32x2{xs[j], j + 1 < len ? xs[j + 1] : 0.0f};
+    for (int e = 0; j < vlen; j += 2, ++e) {
+      const f32x2 xv = f32x2{xs[j], j + 1 < vlen ? xs[j + 1] : 0.0f};
 #pragma unroll
       for (int p = 0; p < kSmemP; ++p)
         in[e & 1][p] = __builtin_elementwise_fma(xv, ld[p], in[e & 1][p]);
@@ -764,40 +957,11 @@ __global__ __launch_bounds__(kBcastThreads) void k_site_bcast_smem(const mi_grou
     flush(in);
   }
 
-  // ---- chunk sum and support flags (vector loads, L2-resident by now) --------------------------
-  // Each lane takes kSmemMaxChunk / kBcastThreads consecutive elements (those within the chunk)
-  // with all its loads in flight at once (a strided loop waits for one L2 round trip per element
-  // group, at the end of every wave).
-  constexpr int kPerLane = kSmemMaxChunk / kBcastThreads;
-  static_assert(kPerLane % 4 == 0, "whole float4 groups per lane");
-  float s_a = 0.0f;
-  {
-    const int e0 = (int)threadIdx.x * kPerLane;
-    const float* xl = xg + i0 + e0;
-    if (e0 + kPerLane <= len && (reinterpret_cast<uintptr_t>(xl) & 15) == 0) {
-      float v[kPerLane];
-#pragma unroll
-      for (int q = 0; q < kPerLane / 4; ++q) {
-        const float4 t = reinterpret_cast<const float4*>(xl)[q];
-        v[4 * q] = t.x;
-        v[4 * q + 1] = t.y;
-        v[4 * q + 2] = t.z;
-        v[4 * q + 3] = t.w;
-      }
-#pragma unroll
-      for (int e = 0; e < kPerLane; ++e) {
-        fl |= !(v[e] == 0.0f || v[e] == 1.0f) ? MI_FLAG_SUPPORT : 0u;
-        s_a += v[e];
-      }
-    } else {
-      for (int e = e0; e < len && e < e0 + kPerLane; ++e) {
-        const float v = xg[i0 + e];
-        fl |= !(v == 0.0f || v == 1.0f) ? MI_FLAG_SUPPORT : 0u;
-        s_a += v;
-      }
-    }
+  // (without the matrix loop the pass runs here, where the chunk is L2-resident)
+  if (!try_matrix) {
+    chunk_pass(std::false_type{});
+    s_a = block_sum(s_a, scratch);
   }
-  s_a = block_sum(s_a, scratch);
   if (SUFF) {
 #pragma unroll
     for (int p = 0; p < kSmemP; ++p) acc[p] = (double)ld[p].x * (double)s_a;
@@ -1379,6 +1543,18 @@ void launch_smem(const mi_group& G, const Plan& p, float* part, uint32_t* flags,
   if (env_int("MININF_AMD_BCAST_SUFFSTAT", 0) != 0)
     hipLaunchKernelGGL((mi::k_site_bcast_smem<FAM, kSmemP, true>), grid, block, 0, s,
                        G, part, p.nseg, gy, rank1, p.chunk, flags, ksum);
+  // MININF_AMD_BCAST_MFMA (default on): the instantiation whose chunks of 0/1 data take the matrix
+  // loop; 0 launches the scalar-load kernel as it was.
+  // No size or alignment threshold: the chunk reaches the matrix cores through LDS, staged by the
+  // chunk-sum pass at any alignment and length, and no shape measured ran slower than the
+  // scalar-load kernel (us per launch with its finalize, replayed, matrix / scalar-load kernel:
+  // K 4096 n 1e6 36.6 / 74.2, the same with x one element off 16-byte alignment 41.5 / 75.3,
+  // K 64 n 1e6 17.0 / 33.4, K 256 n 1e6 17.5 / 33.9, K 64 n 1024 13.9 / 16.8, K 4096 n 4096
+  // 22.0 / 35.0, K 1024 n 65536 19.8 / 32.8; uniform random x, every chunk falling back to the
+  // scalar-load loop at two waves per SIMD, 98.7 / 96.7).
+  else if (env_int("MININF_AMD_BCAST_MFMA", 1) != 0)
+    hipLaunchKernelGGL((mi::k_site_bcast_smem<FAM, kSmemP, false, true>), grid, block, 0, s, G,
+                       part, p.nseg, gy, rank1, p.chunk, flags, ksum);
   else
     hipLaunchKernelGGL((mi::k_site_bcast_smem<FAM, kSmemP>), grid, block, 0, s, G,
                        part, p.nseg, gy, rank1, p.chunk, flags, ksum);

@@ -41,6 +41,8 @@ ELSEWHERE = {
     "JIT_VERBOSE": "read in C++, not through this module: log each specialised compilation",
     "BCAST_SUFFSTAT": "read in C++, not through this module: the sufficient-statistic floor "
                       "measurement of the broadcast site kernel (default 0)",
+    "BCAST_MFMA": "read in C++, not through this module: 0 keeps chunks of 0/1 data off the bf16 "
+                  "matrix cores in the broadcast site kernel (default on; BCAST_SUFFSTAT wins)",
     "ELBO_EXTERNAL": "read in C++, not through this module: take the large ELBO launch's path at "
                      "any size (tests; default 0)",
     "ELBO_KRED": "named in a comment of csrc/elbo.hip only: no code reads it any more",
