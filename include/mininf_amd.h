@@ -822,7 +822,8 @@ int mi_elementwise_entropy(int family, const float* a, int64_t a_stride, const f
                            int64_t b_stride, int64_t N, float* H, float* da, float* db,
                            void* stream);
 
-/* ---- linear-predictor sites (Normal(X @ theta, sigma), Bernoulli(logits = X @ theta)) --------- */
+/* ---- linear-predictor sites (Normal / Bernoulli-logits / Poisson-log / Binomial / NegativeBinomial
+ *      on X @ theta) ---------------------------------------------------------------------------- */
 
 /* A site whose location / logits is the model's own product X @ theta of an observed design matrix
  * X [N, P] and a per-particle coefficient vector theta [K, P] (the reference's regression models:
@@ -832,8 +833,22 @@ int mi_elementwise_entropy(int family, const float* a, int64_t a_stride, const f
  *   dslots[j*K + k] = g0 * d total[k] / d theta[k, j]   for j < P (slot-major: row j holds all k)
  *   dslots[P*K + k] = g0 * d total[k] / d sigma_k       (Normal with per-particle sigma only)
  *   flags[0]        = OR of MI_FLAG_* (value support; sigma > 0; finite predictor)
- * family: MI_NORMAL (sigma = scale[k * scale_stride_k], or scale_constant when scale == NULL) or
- * MI_BERNOULLI_LOGITS (scale unused). P <= MI_LINEAR_MAX_P. */
+ * family: MI_NORMAL (sigma = scale[k * scale_stride_k], or scale_constant when scale == NULL),
+ * MI_BERNOULLI_LOGITS (scale unused), or one of the count regressions on eta = (X theta_k)_i
+ * (scale unused, no slot past the P of theta):
+ *   MI_POISSON            log link, rate = exp(eta):  y eta - exp(eta) - lgamma(y + 1),
+ *                         d/d eta = y - exp(eta); y a non-negative integer
+ *   MI_BINOMIAL           total_count n_i = count, logits = eta (binomial.py:140-158),
+ *                         d/d eta = y - n_i sigmoid(eta); y an integer in [0, n_i]
+ *   MI_NEGATIVE_BINOMIAL  total_count r_i = count, logits = eta (negative_binomial.py:130-150,
+ *                         with its point mass where r_i + y == 0),
+ *                         d/d eta = y - (y + r_i) sigmoid(eta); y a non-negative integer
+ * The terms of a row alone (lgamma(y + 1), the binomial coefficient, NegativeBinomial's
+ * normalisation) are evaluated once per row and added once per particle. MI_FLAG_SUPPORT: y of an
+ * unmasked row outside the support; MI_FLAG_PARAM: a non-finite eta, or on an unmasked row a
+ * negative r_i or a negative or non-integer n_i. The Poisson site is evaluated on eta itself: a
+ * finite eta whose exp overflows float32 follows IEEE (total = -inf, as torch's Poisson(exp(eta)),
+ * no flag), one whose exp underflows keeps y eta finite. P <= MI_LINEAR_MAX_P. */
 #define MI_LINEAR_MAX_P 64
 /* options bit: run the VALU kernel even where the matrix-core (v_mfma_f32_32x32x2_f32) kernel
  * applies (contiguous 16-byte aligned rows of X, P % 4 == 0); for cross-checks. */
@@ -898,6 +913,14 @@ typedef struct mi_linear {
                              written by the launch. dloc / dscale unused. Matrix-core kernel only,
                              P % 4 == 0 (else MI_EUNSUPPORTED: launch mi_normal_rsample first). */
   unsigned long long* stamps; /* as mi_group.stamps: the site kernel's span (timing only) */
+  const float* count;     /* MI_BINOMIAL n_i / MI_NEGATIVE_BINOMIAL r_i at count[i * count_stride_i],
+                             read through row_index / rows exactly as value is; NULL: every row has
+                             count_constant. Data: no gradient, never per particle. Appended to the
+                             struct (mi_linear_struct_size grew; a zeroed tail is a valid Normal /
+                             Bernoulli site) */
+  int64_t count_stride_i;
+  float count_constant;
+  int32_t pad1;
 } mi_linear;
 
 /* *supported = 1 when mi_linear_forward evaluates `site`'s folded prior (the matrix-core kernel). */

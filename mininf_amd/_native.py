@@ -129,6 +129,9 @@ class Linear(ctypes.Structure):
         ("compute_grads", ctypes.c_int32), ("pad0", ctypes.c_int32),
         ("row_index", c_vp), ("rows", Rows), ("prior", Prior), ("draw", Draw),
         ("stamps", c_vp),
+        # Binomial total_count / NegativeBinomial total_count per row, or the constant
+        ("count", c_vp), ("count_stride_i", c_i64),
+        ("count_constant", ctypes.c_float), ("pad1", ctypes.c_int32),
     ]
 
 
@@ -433,6 +436,12 @@ def lib() -> ctypes.CDLL:
         if sizes[1].value != ctypes.sizeof(Elbo):
             raise NativeError(f"{LIB_PATH} lays mi_elbo out in {sizes[1].value} bytes, this binding "
                               f"in {ctypes.sizeof(Elbo)}; rebuild it (mininf_amd/build.py --force).")
+        # (mi_linear grew within ABI 18 too: the count operand of the count regressions)
+        linear = ctypes.c_size_t()
+        handle.mi_linear_struct_size(ctypes.byref(linear))
+        if linear.value != ctypes.sizeof(Linear):
+            raise NativeError(f"{LIB_PATH} lays mi_linear out in {linear.value} bytes, this binding "
+                              f"in {ctypes.sizeof(Linear)}; rebuild it (mininf_amd/build.py --force).")
         _LIB = handle
     return _LIB
 

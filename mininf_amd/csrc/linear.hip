@@ -1,5 +1,6 @@
-// Linear-predictor sites: Normal(X @ theta, sigma) and Bernoulli(logits = X @ theta) with the
-// product evaluated inside the site kernel.
+// Linear-predictor sites: Normal(X @ theta, sigma), Bernoulli(logits = X @ theta) and the count
+// regressions Poisson(exp(X @ theta)), Binomial(n, logits = X @ theta) and
+// NegativeBinomial(r, logits = X @ theta), with the product evaluated inside the site kernel.
 //
 // In the reference's regression models (tests/test_mininf.py:13-18, examples/minibatch.md:24-33)
 // the model computes `X @ theta` and hands the result to a Normal site; traced over K particles
@@ -26,6 +27,79 @@ namespace mi {
 constexpr int kLinThreads = 256;
 constexpr int kLinChunk = 64;
 
+// ---- count regressions ---------------------------------------------------------------------------
+// With eta = <X_i, theta_k>, T_i the row's total (Binomial n_i, NegativeBinomial r_i + y_i) and c_i
+// the terms of the row alone:
+//   Poisson            log p = y eta - exp(eta) + c,   c = -lgamma(y + 1)       d/d eta = y - exp(eta)
+//   Binomial           log p = (eta >= 0 ? y - T : y) eta - T log1p(exp(-|eta|)) + c,
+//                      c = lgamma(n + 1) - lgamma(y + 1) - lgamma(n - y + 1)   d/d eta = y - T sigmoid(eta)
+//   NegativeBinomial   the same two expressions with y - T = -r (staged as -r, exactly) and
+//                      c = lgamma(r + y) - lgamma(1 + y) - lgamma(r), 0 where r + y == 0
+// (eval_binomial / eval_negative_binomial of device_math.hpp, written on their common parts: for
+// eta >= 0, r logsigmoid(-eta) + y logsigmoid(eta) = -r eta - (r + y) log1p(exp(-eta)).) The two
+// logit families therefore share one kernel instantiation (FAMILY = MI_BINOMIAL): they differ only
+// where a row is staged, behind a branch on mi_linear.family that is uniform over the launch. c_i is
+// evaluated once per staged row, summed by the staging threads and added once per particle; the
+// per-(row, particle) step is one exp (Poisson) or the exp / log / rcp of the Bernoulli site.
+constexpr bool lin_counted(int family) { return family == MI_BINOMIAL; }   // stages (T, y - T)
+constexpr bool lin_row_terms(int family) { return family == MI_POISSON || family == MI_BINOMIAL; }
+
+// LDS of the counted families' rows, in an array of their own: the other instantiations keep
+// their layout.
+template <bool ON, int ROWS>
+__device__ __forceinline__ float2* count_lds() {
+  if constexpr (ON) {
+    __shared__ float2 buf[ROWS];
+    return buf;
+  } else {
+    return nullptr;
+  }
+}
+
+// One staged row of a count regression: (y, T, y - T, c), all zero for a masked-out row (which then
+// adds nothing for any finite eta), and the row's flags.
+struct CountRow {
+  float y, t, a, c;
+};
+template <int FAMILY>
+__device__ __forceinline__ CountRow count_row(int family, float y, float n, bool observed,
+                                              uint32_t& fl) {
+  CountRow r{0.0f, 0.0f, 0.0f, 0.0f};
+  if (!observed) return r;
+  bool support = y >= 0.0f && y == floorf(y);
+  bool param = true;
+  r.y = y;
+  if (FAMILY == MI_POISSON) {
+    r.c = -lgammaf(y + 1.0f);
+  } else if (family == MI_BINOMIAL) {
+    support = support && y <= n;
+    param = n >= 0.0f && n == floorf(n);
+    r.t = n;
+    r.a = y - n;
+    r.c = lgammaf(n + 1.0f) - lgammaf(y + 1.0f) - lgammaf(n - y + 1.0f);
+  } else {
+    param = n >= 0.0f;
+    r.t = n + y;
+    r.a = -n;
+    r.c = (n + y == 0.0f) ? 0.0f : lgammaf(n + y) - lgammaf(1.0f + y) - lgammaf(n);
+  }
+  fl |= (support ? 0u : MI_FLAG_SUPPORT) | (param ? 0u : MI_FLAG_PARAM);
+  return r;
+}
+
+// The per-(row, particle) step of the logit count families: log p without c, and d/d eta.
+__device__ __forceinline__ void count_logit_elem(float eta, float y, float t, float a, float& lp,
+                                                 float& d) {
+  const float e = fast_exp(-fabsf(eta));
+  const float u = 1.0f + e;
+  const float ru = rcp(u);
+  const float sig = eta >= 0.0f ? ru : e * ru;
+  lp = fmaf(eta >= 0.0f ? a : y, eta, -(t * log1p_unit(e, u, ru)));
+  d = fmaf(-t, sig, y);
+}
+
+__device__ __forceinline__ bool non_finite(float x) { return !(fabsf(x) < __builtin_inff()); }
+
 template <int FAMILY, int PMAX>
 __global__ __launch_bounds__(kLinThreads) void k_linear(const mi_linear L, int kb,
                                                         int64_t rows_per_tile, int64_t ntile,
@@ -35,6 +109,8 @@ __global__ __launch_bounds__(kLinThreads) void k_linear(const mi_linear L, int k
   __shared__ float ys[kLinChunk];
   __shared__ float ms[kLinChunk];
   __shared__ float red[kLinThreads];
+  float2* const cts = count_lds<lin_counted(FAMILY), kLinChunk>();   // (T, y - T) of the chunk's rows
+  double rowc = 0.0;   // the staging threads' sums of their rows' c (fp64, as in k_linear_mfma)
   const int tid = threadIdx.x;
   const int kk = tid & (kb - 1);
   const int g = tid / kb;
@@ -76,12 +152,22 @@ __global__ __launch_bounds__(kLinThreads) void k_linear(const mi_linear L, int k
     }
     for (int r = tid; r < kLinChunk; r += kLinThreads) {
       float y = 0.0f, m = 0.0f;
+      float n = 0.0f;
       if (r < rows) {
         const int64_t i = L.row_index != nullptr ? L.row_index[c0 + r] : c0 + r;
         y = L.value[i * L.value_stride_i];
         m = (L.mask == nullptr || L.mask[i * L.mask_stride_i] != 0) ? 1.0f : 0.0f;
-        const bool bad = FAMILY == MI_NORMAL ? (y != y) : !(y == 0.0f || y == 1.0f);
-        fl |= (m != 0.0f && bad) ? MI_FLAG_SUPPORT : 0u;
+        if constexpr (lin_counted(FAMILY))
+          n = L.count != nullptr ? L.count[i * L.count_stride_i] : L.count_constant;
+        if constexpr (!lin_row_terms(FAMILY)) {
+          const bool bad = FAMILY == MI_NORMAL ? (y != y) : !(y == 0.0f || y == 1.0f);
+          fl |= (m != 0.0f && bad) ? MI_FLAG_SUPPORT : 0u;
+        }
+      }
+      if constexpr (lin_row_terms(FAMILY)) {
+        const CountRow cr = count_row<FAMILY>(L.family, y, n, m != 0.0f, fl);
+        rowc += (double)cr.c;
+        if constexpr (lin_counted(FAMILY)) cts[r] = make_float2(cr.t, cr.a);
       }
       ys[r] = m != 0.0f ? y : 0.0f;   // masked-out values (NaN in missing data) are never used
       ms[r] = m;
@@ -104,7 +190,18 @@ __global__ __launch_bounds__(kLinThreads) void k_linear(const mi_linear L, int k
       }
       const float loc = (l0 + l1) + (l2 + l3);
       float gl;
-      if (FAMILY == MI_NORMAL) {
+      if constexpr (FAMILY == MI_POISSON) {
+        const float e = m != 0.0f ? fast_exp(loc) : 0.0f;   // (y is staged as 0 under the mask)
+        lp += fmaf(y, loc, -e);
+        gl = y - e;
+        fl |= non_finite(loc) ? MI_FLAG_PARAM : 0u;
+      } else if constexpr (FAMILY == MI_BINOMIAL) {
+        const float2 ta = cts[r];
+        float l;
+        count_logit_elem(loc, y, ta.x, ta.y, l, gl);
+        lp += l;
+        fl |= non_finite(loc) ? MI_FLAG_PARAM : 0u;
+      } else if (FAMILY == MI_NORMAL) {
         const float z = (y - loc) * inv;
         lp = fmaf(m, fmaf(-0.5f * z, z, cst), lp);
         gl = z * inv;
@@ -151,6 +248,16 @@ __global__ __launch_bounds__(kLinThreads) void k_linear(const mi_linear L, int k
   // v = 0 log p, 1..P dtheta_j, P + 1 dsigma.
   const int nv = 1 + P + (per_particle_sigma ? 1 : 0);
   const int64_t tile = blockIdx.x;
+  float rowsum = 0.0f;   // the tile's rows' c, the same for every particle
+  if constexpr (lin_row_terms(FAMILY)) {
+    // (threads past the chunk staged none; the staging threads' fp64 sums through LDS as two words)
+    __shared__ double rowsums[kLinChunk];
+    if (tid < kLinChunk) rowsums[tid] = rowc;
+    __syncthreads();
+    double s = 0.0;
+    for (int q = 0; q < kLinChunk; ++q) s += rowsums[q];
+    rowsum = (float)s;
+  }
 #pragma unroll
   for (int v = 0; v < PMAX + 2; ++v) {
     if (v < nv) {
@@ -161,6 +268,7 @@ __global__ __launch_bounds__(kLinThreads) void k_linear(const mi_linear L, int k
       if (g == 0 && kok) {
         float s = 0.0f;
         for (int q = 0; q < G; ++q) s += red[q * kb + kk];
+        if constexpr (lin_row_terms(FAMILY)) s += v == 0 ? rowsum : 0.0f;
         part[((int64_t)v * ntile + tile) * K + k] = s;
       }
     }
@@ -302,6 +410,8 @@ __global__ __launch_bounds__(NT, MINW) void k_linear_mfma(const mi_linear L, int
   __shared__ float2 yms[S::CH];
   // rows drawn here (mi_linear.rows, ONESTAGE launches only): the stage's dataset rows
   __shared__ int32_t grows[ONESTAGE ? S::CH : 1];
+  float2* const cts = count_lds<lin_counted(FAMILY), S::CH>();   // (T, y - T) of the stage's rows
+  double rowc = 0.0;   // threads tid < CH: the sum of c over the rows they staged
   const bool gen_rows = ONESTAGE && L.rows.counter != nullptr;
   uint64_t batch_no = 0;
 
@@ -358,6 +468,7 @@ __global__ __launch_bounds__(NT, MINW) void k_linear_mfma(const mi_linear L, int
   float4 xq[S::QPT];
   float yraw = 0.0f;          // the stage's (y, mask) of row tid, as loaded
   uint32_t mraw = 1u;
+  float nraw = 0.0f;          // and its count (Binomial, NegativeBinomial)
   int64_t staged_row0 = 0;    // the stage whose loads xq / yraw / mraw hold
   // Source rows first (one uniform branch on how rows are given), then every X quad and the
   // (y, mask) of the stage issued together with no wait in between: a guarded load per quad
@@ -391,6 +502,8 @@ __global__ __launch_bounds__(NT, MINW) void k_linear_mfma(const mi_linear L, int
     }
     yraw = L.value[src[S::QPT] * L.value_stride_i];
     mraw = L.mask == nullptr ? 1u : (uint32_t)L.mask[src[S::QPT] * L.mask_stride_i];
+    if constexpr (lin_counted(FAMILY))
+      nraw = L.count != nullptr ? L.count[src[S::QPT] * L.count_stride_i] : L.count_constant;
     staged_row0 = row0;
   };
   // The loads' values are first used here (rows past N and features past P zeroed, the (y, mask)
@@ -415,8 +528,15 @@ __global__ __launch_bounds__(NT, MINW) void k_linear_mfma(const mi_linear L, int
       if (row < N) {
         y = yraw;
         m = mraw != 0u ? 1.0f : 0.0f;
-        const bool bad = FAMILY == MI_NORMAL ? (y != y) : !(y == 0.0f || y == 1.0f);
-        fl |= (m != 0.0f && bad) ? MI_FLAG_SUPPORT : 0u;
+        if constexpr (!lin_row_terms(FAMILY)) {
+          const bool bad = FAMILY == MI_NORMAL ? (y != y) : !(y == 0.0f || y == 1.0f);
+          fl |= (m != 0.0f && bad) ? MI_FLAG_SUPPORT : 0u;
+        }
+      }
+      if constexpr (lin_row_terms(FAMILY)) {
+        const CountRow cr = count_row<FAMILY>(L.family, y, nraw, m != 0.0f, fl);
+        rowc += (double)cr.c;
+        if constexpr (lin_counted(FAMILY)) cts[tid] = make_float2(cr.t, cr.a);
       }
       yms[tid] = make_float2(m != 0.0f ? y : 0.0f, m);
     }
@@ -467,8 +587,20 @@ __global__ __launch_bounds__(NT, MINW) void k_linear_mfma(const mi_linear L, int
       const int row = tile * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
       const float2 ym = yms[row];
       const float loc = mu[r];
-      fl |= (loc != loc) ? MI_FLAG_PARAM : 0u;
-      if (FAMILY == MI_NORMAL) {
+      if constexpr (lin_row_terms(FAMILY)) fl |= non_finite(loc) ? MI_FLAG_PARAM : 0u;
+      else fl |= (loc != loc) ? MI_FLAG_PARAM : 0u;
+      if constexpr (FAMILY == MI_POISSON) {
+        const float e = ym.y != 0.0f ? fast_exp(loc) : 0.0f;   // (y is staged as 0 under the mask)
+        lpt += fmaf(ym.x, loc, -e);
+        mu[r] = ym.x - e;
+      } else if constexpr (FAMILY == MI_BINOMIAL) {
+        // (y, T and y - T are staged as 0 under the mask: such a row adds nothing)
+        const float2 ta = cts[row];
+        float l, d;
+        count_logit_elem(loc, ym.x, ta.x, ta.y, l, d);
+        lpt += l;
+        mu[r] = d;
+      } else if (FAMILY == MI_NORMAL) {
         const float d = ym.y * (ym.x - loc);
         lpt = fmaf(d, d, lpt);
         cnt += ym.y;
@@ -598,6 +730,22 @@ __global__ __launch_bounds__(NT, MINW) void k_linear_mfma(const mi_linear L, int
   const float wscale = (float)L.site_scale;
   lpd += __shfl_xor(lpd, 32, kWave);
   cnt += __shfl_xor(cnt, 32, kWave);
+  if constexpr (lin_row_terms(FAMILY)) {
+    // the block's rows' c, summed over the staging threads in a fixed order and added once per
+    // particle: to the tile that the first row subset writes (or the combined one)
+    __shared__ double rowsums[S::CH / kWave > 0 ? S::CH / kWave : 1];
+    constexpr int kStageWaves = S::CH / kWave;
+    static_assert(S::CH % kWave == 0 && kStageWaves >= 1 && kStageWaves <= kMfWaves, "staging waves");
+    double v = rowc;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
+    if (lane == 0 && wave < kStageWaves) rowsums[wave] = v;
+    __syncthreads();
+    if (rs == 0) {
+#pragma unroll
+      for (int w = 0; w < kStageWaves; ++w) lpd += rowsums[w];
+    }
+  }
   val[16 * PT] = val[16 * PT + 1] = 0.0f;
   if (h == 0 && k0 + c < K) {
     const int64_t kk = k0 + c;
@@ -769,7 +917,8 @@ bool valid(const mi_linear* L) {
        L->prior.flags == nullptr || !(L->site_scale != 0.0)))
     return false;
   return L != nullptr && L->K >= 1 && L->N >= 1 && L->P >= 1 && L->P <= MI_LINEAR_MAX_P &&
-         (L->family == MI_NORMAL || L->family == MI_BERNOULLI_LOGITS) && L->x != nullptr &&
+         (L->family == MI_NORMAL || L->family == MI_BERNOULLI_LOGITS || L->family == MI_POISSON ||
+          L->family == MI_BINOMIAL || L->family == MI_NEGATIVE_BINOMIAL) && L->x != nullptr &&
          L->theta != nullptr && L->value != nullptr;
 }
 
@@ -807,6 +956,7 @@ int mf_variant(int pt) { return pt == 1 ? 0 : 1; }
 
 Geometry geometry(const mi_linear* L) {
   Geometry g{};
+  // value, dtheta and, for a Normal with a sigma per particle only, dsigma
   g.nv = 1 + (int)L->P + ((L->family == MI_NORMAL && L->scale != nullptr) ? 1 : 0);
   g.mfma = use_mfma(L);
   if (g.mfma) {
@@ -992,8 +1142,12 @@ int mi_linear_forward_deferred(const mi_linear* site, void* workspace, size_t wo
     return to_code(e);
   if (site->family == MI_NORMAL)
     launch<MI_NORMAL>(*site, g, part, flags, s);
-  else
+  else if (site->family == MI_BERNOULLI_LOGITS)
     launch<MI_BERNOULLI_LOGITS>(*site, g, part, flags, s);
+  else if (site->family == MI_POISSON)
+    launch<MI_POISSON>(*site, g, part, flags, s);
+  else   // Binomial and NegativeBinomial: one instantiation (count_row tells them apart)
+    launch<MI_BINOMIAL>(*site, g, part, flags, s);
   e = hipGetLastError();
   if (e != hipSuccess) return to_code(e);
   if (stop_event != nullptr && (e = mi_record_event(stop_event, s)) != hipSuccess)

@@ -1,6 +1,7 @@
 """
-Linear-predictor sites: Normal(X @ theta, sigma) / Bernoulli(logits = X @ theta), fused
-(``mi_linear_forward``).
+Linear-predictor sites: Normal(X @ theta, sigma) / Bernoulli(logits = X @ theta) and the count
+regressions Poisson(exp(X @ theta)) / Binomial(n, logits = X @ theta) /
+NegativeBinomial(r, logits = X @ theta), fused (``mi_linear_forward``).
 """
 from __future__ import annotations
 
@@ -23,7 +24,7 @@ class _LinearLauncher:
     """
     def __init__(self, site: SiteRecord, K: int, g0: float, device: torch.device,
                  theta: torch.Tensor, sigma: Optional[_View], value: _View,
-                 mask: Optional[torch.Tensor]) -> None:
+                 mask: Optional[torch.Tensor], count: Optional[_View] = None) -> None:
         self.site, self.K, self.g0, self.device = site, K, g0, device
         self.X = site.linear_X
         self.N, self.P = self.X.shape
@@ -31,6 +32,9 @@ class _LinearLauncher:
         # columns of X and the value, and the batch's rows
         self.batch: Optional["data._Batch"] = None
         self.X_src, self.value_src = self.X, None
+        # Binomial / NegativeBinomial total_count: a constant, a [N] view, or (minibatch) the
+        # dataset column the batch's rows index
+        self.count, self.count_src = count, None
         self.theta = theta
         self.sigma = sigma
         self.sigma_input = None
@@ -92,6 +96,16 @@ class _LinearLauncher:
             data.ensure_filled(self.value.tensor)
             L.value = self.value.tensor.data_ptr()
             L.value_stride_i = self.value.si
+        if self.count is not None:
+            if self.count.constant is not None:
+                L.count_constant = self.count.constant
+            elif self.batch is not None:
+                L.count = self.count_src.data_ptr()
+                L.count_stride_i = self.count_src.stride(0)
+            else:
+                data.ensure_filled(self.count.tensor)
+                L.count = self.count.tensor.data_ptr()
+                L.count_stride_i = self.count.si
         if self.mask is not None:
             L.mask = self.mask.data_ptr()
             L.mask_stride_i = self.mask.stride(0) if self.N > 1 else 1

@@ -138,8 +138,9 @@ def plan_linear(trace: ParticleTrace, g0: float, device: torch.device,
                 claims: Optional[Dict[int, guide.PendingDraw]] = None) -> List[_LinearLauncher]:
     """
     Launchers for the fused linear-predictor sites of a trace. A site whose operands the kernel
-    cannot take (per-element sigma, particle-dependent values, non-float32) gets its predictor
-    materialised here as ``theta @ X.T`` and is planned like any other site.
+    cannot take (per-element sigma, particle-dependent values or counts, non-float32) gets its
+    predictor materialised here as ``theta @ X.T`` (``exp`` of it for a Poisson site, whose role is
+    the rate) and is planned like any other site.
     """
     K = trace.K
     out: List[_LinearLauncher] = []
@@ -151,6 +152,11 @@ def plan_linear(trace: ParticleTrace, g0: float, device: torch.device,
         launcher = None
         ok = theta is not None and theta.dtype == torch.float32 and theta.dim() == 2 and \
             theta.device == device and site.linear_X.device == device
+        counted = site.family in ("binomial", "negative_binomial")
+        if site.family in _INTEGER_VALUED and not (
+                site.tensors[-1].dtype == torch.float32 and
+                (not counted or site.tensors[0].dtype == torch.float32)):
+            ok = False   # integer tensors: the site-group path converts them
         if ok:
             value_t, const = _to_device(_float(site.tensors[-1], site.name), K, device,
                                         f"site '{site.name}'", allow_constant=False)
@@ -164,22 +170,36 @@ def plan_linear(trace: ParticleTrace, g0: float, device: torch.device,
                     ok = False
             if value.sk != 0:
                 ok = False
+            count = None
+            if counted:
+                t, c = _to_device(site.tensors[0], K, device, f"site '{site.name}'")
+                count = _View(None, 0, 0, c) if c is not None else _collapse(t, K, shape)
+                if count.constant is None and (count.sk != 0 or count.tensor.requires_grad):
+                    ok = False   # a total_count per particle (a latent dispersion)
             mask = None
             if site.mask is not None:
                 mask = site.mask.to(device).bool().expand(shape).reshape(-1)
             if ok:
-                launcher = _LinearLauncher(site, K, g0, device, theta, sigma, value, mask)
+                launcher = _LinearLauncher(site, K, g0, device, theta, sigma, value, mask, count)
                 xb, vb = data.lookup(site.linear_X), data.lookup(value.tensor)
+                # (a per-row count joins a minibatch only as a column of the same loader)
+                cb = data.lookup(count.tensor) if count is not None and count.constant is None \
+                    else None
+                count_ok = count is None or count.constant is not None or \
+                    (cb is not None and xb is not None and cb[0] is xb[0] and count.si == 1)
                 if xb is not None and vb is not None and xb[0] is vb[0] and mask is None and \
-                        value.si == 1:
+                        value.si == 1 and count_ok:
                     batch = xb[0]
                     launcher.batch = batch
                     launcher.X_src = batch.loader.columns[xb[1]]
                     launcher.value_src = batch.loader.columns[vb[1]]
+                    if cb is not None:
+                        launcher.count_src = batch.loader.columns[cb[1]]
         if launcher is None:
             # materialise the predictor as the model would have: [K, N] = theta @ X^T
             guide.flush_draws(claimed=True)
-            site.tensors[0] = theta @ site.linear_X.t()
+            real = theta @ site.linear_X.t()
+            site.tensors[site.linear_role] = real.exp() if site.linear_link == "exp" else real
             site.linear_X = None
             continue
         launcher.draw = (claims or {}).get(id(site))

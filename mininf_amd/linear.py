@@ -8,7 +8,11 @@ model, :class:`DeferredMatmul` (a ``TorchFunctionMode``) intercepts ``matmul(X, 
 observed 2-D ``X`` and a per-particle 1-D ``theta`` and returns a *placeholder*: a batched tensor of
 the right shape backed by a zero-stride zero, costing no memory and no kernel. The particle tracer
 turns a Normal / Bernoulli-logits site whose location / logits is such a placeholder into a fused
-linear site (``mi_linear_forward``: the product is evaluated inside the site kernel).
+linear site (``mi_linear_forward``: the product is evaluated inside the site kernel). So are the
+count regressions: a Binomial / NegativeBinomial whose ``logits`` is a placeholder, and a Poisson
+whose ``rate`` is ``exp`` of one -- ``torch.exp`` / ``Tensor.exp`` of a placeholder is a placeholder
+tagged with the *link* ``exp`` (the log link of the regression), which materialises to ``exp`` of
+the real product.
 
 Semantics are preserved for every other use: any torch operation that reads a placeholder's values
 (anything but shape queries and broadcasting views) first *materialises* it -- the real
@@ -42,7 +46,10 @@ _METADATA = {
     torch.Tensor.is_leaf.__get__, torch.Tensor.names.__get__,
 }
 
-# Broadcasting views of a placeholder are placeholders of the broadcast shape.
+# exp of an identity-link placeholder is a placeholder with the link "exp" (Poisson's log link).
+_EXPS = {torch.exp, torch.Tensor.exp}
+
+# Broadcasting views of a placeholder are placeholders of the broadcast shape (and the same link).
 _BROADCASTS = {torch.broadcast_tensors, torch.Tensor.expand, torch.Tensor.expand_as,
                torch.Tensor.broadcast_to, torch.broadcast_to}
 
@@ -72,13 +79,15 @@ def _leaves(args, kwargs):
 class Deferred:
     """
     ``root``: the deferred ``X @ theta`` (``X`` [N, P] observed, ``theta`` batched [P]); a derived
-    placeholder is ``root`` broadcast to ``shape``.
+    placeholder is ``root`` broadcast to ``shape``, then passed through ``link`` ("identity" or
+    "exp").
     """
     X: torch.Tensor
     theta: torch.Tensor
     shape: torch.Size
     root: Optional["Deferred"] = None
     real: Optional[torch.Tensor] = None
+    link: str = "identity"
 
 
 class DeferredMatmul(TorchFunctionMode):
@@ -149,6 +158,8 @@ class DeferredMatmul(TorchFunctionMode):
             self._bypass = True
             try:
                 info.real = root.real.expand(info.shape)
+                if info.link == "exp":
+                    info.real = info.real.exp()
             finally:
                 self._bypass = False
         return info.real
@@ -182,6 +193,11 @@ class DeferredMatmul(TorchFunctionMode):
             return func(*args, **kwargs)
         if func in _METADATA:
             return func(*args, **kwargs)
+        if func is torch.Tensor.type_as and len(args) == 2 and self.lookup(args[0]) is None and \
+                lazy_of(args[0]) is None:
+            # `x.type_as(placeholder)` reads the placeholder's dtype and device only (Binomial and
+            # NegativeBinomial cast their total_count to their logits' type this way)
+            return func(*args, **kwargs)
         if lazy and func not in _BROADCASTS:
             raise NeedsDraws(getattr(func, "__name__", str(func)))
         if not touched:
@@ -197,6 +213,12 @@ class DeferredMatmul(TorchFunctionMode):
             else:
                 self._derive(args[0], out)
             return out
+        if func in _EXPS and len(args) == 1 and not kwargs and touched[0].link == "identity":
+            info = touched[0]
+            root = info.root or info
+            derived = Deferred(X=root.X, theta=root.theta, shape=torch.Size(args[0].shape),
+                               root=root, link="exp")
+            return self._placeholder(args[0], derived.shape, derived)
         args, kwargs = tree_map(lambda x: self.materialize(x) if self.lookup(x) else x,
                                 (args, kwargs))
         return func(*args, **kwargs)
@@ -207,5 +229,5 @@ class DeferredMatmul(TorchFunctionMode):
             return
         root = info.root or info
         self.deferred[id(dst)] = Deferred(X=root.X, theta=root.theta,
-                                          shape=torch.Size(dst.shape), root=root)
+                                          shape=torch.Size(dst.shape), root=root, link=info.link)
         self._keep.append(dst)

@@ -114,6 +114,8 @@ class SiteRecord:
     linear_X: Optional[torch.Tensor] = None
     linear_theta_index: int = -1
     linear_theta: Optional[torch.Tensor] = None
+    linear_role: int = 0      # the role that is the deferred predictor (Binomial families: 1)
+    linear_link: str = ""     # "identity", or "exp" (a Poisson rate: the log link)
     order: int = 0   # position of the sample statement in the model (errors raise in this order)
     extra: float = 0.0   # the family's constant fourth input (mi_site.extra): StudentT's df
 
@@ -566,17 +568,27 @@ class ParticleTracer(TracerMixin):
             return value
 
         # A deferred `X @ theta` as the location / logits of a Normal / Bernoulli-logits site over
-        # shared data becomes a fused linear site; every other deferred parameter is materialised.
+        # shared data becomes a fused linear site, and so do the count regressions: a Poisson whose
+        # rate is exp of it (the "exp" link), a Binomial / NegativeBinomial built with `logits=` it
+        # and a total_count that is data. Every other deferred parameter is materialised.
         linear = None
+        role, link = 0, ""
         mode = self.deferred
         if mode is not None:
-            info = mode.lookup(params[0]) if params else None
-            if info is not None and family in ("normal", "bernoulli_logits") and \
+            if family in ("binomial", "negative_binomial"):
+                role = 1
+                eligible = "logits" in distribution.__dict__ and not is_batched(params[0])
+            else:
+                eligible = family in ("normal", "bernoulli_logits", "poisson")
+            info = mode.lookup(params[role]) if params else None
+            if info is not None and eligible and \
+                    info.link == ("exp" if family == "poisson" else "identity") and \
                     not is_batched(data) and tuple(shape) == (info.X.shape[0],) and \
                     tuple(data.shape) == tuple(shape) and \
-                    all(mode.lookup(p) is None for p in params[1:]):
+                    all(mode.lookup(p) is None for j, p in enumerate(params) if j != role):
                 linear = info.root or info
-            params = [p if (linear is not None and j == 0) else mode.materialize(p)
+                link = info.link
+            params = [p if (linear is not None and j == role) else mode.materialize(p)
                       for j, p in enumerate(params)]
             if family in ("dirichlet", "mixture_normal"):
                 data = mode.materialize(data)
@@ -590,6 +602,7 @@ class ParticleTracer(TracerMixin):
         if linear is not None:
             record.linear_X = linear.X
             record.linear_theta_index = self._emit(linear.theta)
+            record.linear_role, record.linear_link = role, link
         self.sites.append(record)
         return value
 
