@@ -936,6 +936,58 @@ int mi_linear_forward_deferred(const mi_linear* site, void* workspace, size_t wo
                                float* total, float* dslots, uint32_t* flags, void* start_event,
                                void* stop_event, void* stream, mi_reduce* reduce);
 
+/* ---- softmax regression sites (Categorical(logits = X @ Theta)) --------------------------------- */
+
+/* A Categorical site whose logits are the model's own product X @ Theta of an observed design
+ * matrix X [N, P] and a per-particle coefficient matrix Theta [K, P, C] (multinomial logistic
+ * regression). The product is evaluated inside the site kernel (v_mfma_f32_32x32x2_f32), so the
+ * [K, N, C] logits and their gradient never exist in memory. With eta_c = sum_p X[i, p]
+ * Theta[k, p, c], m = max_c eta_c and lse = m + log sum_c exp(eta_c - m):
+ *   total[k]        = site_scale * sum_i mask_i * (eta_{y_i} - lse)
+ *   dtheta[k, p, c] = g0 * site_scale * sum_i mask_i * ([c == y_i] - exp(eta_c - lse)) * X[i, p]
+ * (dtheta contiguous [K, P, C], every entry written; not written when NULL). flags[0] (zeroed by
+ * the call unless options has MI_GROUP_FLAGS_ZEROED): MI_FLAG_SUPPORT for an observed row whose
+ * label is outside [0, C) or (float labels) non-integer or NaN, MI_FLAG_PARAM for a non-finite eta
+ * on an observed row; a masked-out row adds nothing and sets no flag, whatever its label holds.
+ * MI_EINVAL: a NULL site, x, theta, value, total or flags; K, N, P or C < 1; P > MI_LINEAR_MAX_P;
+ * C > MI_SOFTMAX_LINEAR_MAX_C; an unknown value_kind. MI_EWORKSPACE: a workspace smaller than
+ * mi_softmax_linear_workspace_bytes asks for. All checked before any device work. */
+#define MI_SOFTMAX_LINEAR_MAX_C 32
+#define MI_SOFTMAX_LABEL_INT64 0
+#define MI_SOFTMAX_LABEL_FLOAT32 1
+
+typedef struct mi_softmax_linear {
+  int64_t K;
+  int64_t N;
+  int64_t P;
+  int64_t C;
+  const float* x;         /* X[i, j] at x[i * x_stride_i + j * x_stride_j] */
+  int64_t x_stride_i;
+  int64_t x_stride_j;
+  const float* theta;     /* Theta[k, j, c] at theta[k * stride_k + j * stride_j + c * stride_c] */
+  int64_t theta_stride_k;
+  int64_t theta_stride_j;
+  int64_t theta_stride_c;
+  const void* value;      /* labels: int64 or float32 (value_kind) at value[i * value_stride_i] */
+  int64_t value_stride_i;
+  int32_t value_kind;     /* MI_SOFTMAX_LABEL_* */
+  int32_t options;        /* MI_GROUP_FLAGS_ZEROED */
+  const uint8_t* mask;    /* NULL or mask[i * mask_stride_i] */
+  int64_t mask_stride_i;
+  const int32_t* row_index; /* NULL, or row i of the site reads row row_index[i] of x, value and
+                               mask (as mi_linear.row_index) */
+  double site_scale;      /* minibatch scale (core.py:267-271) */
+  float grad_scale;       /* g0 */
+  int32_t pad0;
+} mi_softmax_linear;
+
+int mi_softmax_linear_struct_size(size_t* bytes);
+int mi_softmax_linear_workspace_bytes(const mi_softmax_linear* site, size_t* bytes);
+int mi_softmax_linear_forward(const mi_softmax_linear* site, void* workspace,
+                              size_t workspace_bytes, float* total /* [K] */,
+                              float* dtheta /* [K, P, C] contiguous or NULL */, uint32_t* flags,
+                              void* stream);
+
 /* ---- device-resident minibatches (replaces examples/minibatch.md:78-88, the host DataLoader) ---- */
 
 /* Row indices of the next minibatch of an n-row dataset: with c = counter[0] (then counter[0] =

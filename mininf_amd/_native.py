@@ -135,6 +135,26 @@ class Linear(ctypes.Structure):
     ]
 
 
+SOFTMAX_LINEAR_MAX_C = 32   # MI_SOFTMAX_LINEAR_MAX_C
+SOFTMAX_LABEL_INT64, SOFTMAX_LABEL_FLOAT32 = 0, 1
+
+
+class SoftmaxLinear(ctypes.Structure):
+    """mi_softmax_linear (include/mininf_amd.h)."""
+    _fields_ = [
+        ("K", c_i64), ("N", c_i64), ("P", c_i64), ("C", c_i64),
+        ("x", c_vp), ("x_stride_i", c_i64), ("x_stride_j", c_i64),
+        ("theta", c_vp), ("theta_stride_k", c_i64), ("theta_stride_j", c_i64),
+        ("theta_stride_c", c_i64),
+        ("value", c_vp), ("value_stride_i", c_i64),
+        ("value_kind", ctypes.c_int32), ("options", ctypes.c_int32),
+        ("mask", c_vp), ("mask_stride_i", c_i64),
+        ("row_index", c_vp),
+        ("site_scale", ctypes.c_double),
+        ("grad_scale", ctypes.c_float), ("pad0", ctypes.c_int32),
+    ]
+
+
 class Source(ctypes.Structure):
     _fields_ = [("ptr", c_vp), ("stride_k", c_i64), ("stride_i", c_i64)]
 
@@ -378,6 +398,11 @@ _SIGNATURES = {
     "mi_linear_forward_deferred": (ctypes.c_int, [ctypes.POINTER(Linear), c_vp, ctypes.c_size_t,
                                                   c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                                   ctypes.POINTER(Reduce)]),
+    "mi_softmax_linear_struct_size": (ctypes.c_int, [ctypes.POINTER(ctypes.c_size_t)]),
+    "mi_softmax_linear_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(SoftmaxLinear),
+                                                         ctypes.POINTER(ctypes.c_size_t)]),
+    "mi_softmax_linear_forward": (ctypes.c_int, [ctypes.POINTER(SoftmaxLinear), c_vp,
+                                                 ctypes.c_size_t, c_vp, c_vp, c_vp, c_vp]),
     "mi_minibatch_rows": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, ctypes.c_int32,
                                          ctypes.c_uint64, c_vp, c_i64, c_vp]),
     "mi_gather_rows": (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
@@ -442,6 +467,12 @@ def lib() -> ctypes.CDLL:
         if linear.value != ctypes.sizeof(Linear):
             raise NativeError(f"{LIB_PATH} lays mi_linear out in {linear.value} bytes, this binding "
                               f"in {ctypes.sizeof(Linear)}; rebuild it (mininf_amd/build.py --force).")
+        softmax = ctypes.c_size_t()
+        handle.mi_softmax_linear_struct_size(ctypes.byref(softmax))
+        if softmax.value != ctypes.sizeof(SoftmaxLinear):
+            raise NativeError(f"{LIB_PATH} lays mi_softmax_linear out in {softmax.value} bytes, this "
+                              f"binding in {ctypes.sizeof(SoftmaxLinear)}; rebuild it "
+                              "(mininf_amd/build.py --force).")
         _LIB = handle
     return _LIB
 

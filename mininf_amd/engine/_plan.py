@@ -18,6 +18,7 @@ from ..particles import ParticleTrace, SiteRecord
 from ._groups import _QUERY_ADDRESS, _GroupLauncher
 from ._held import flush_pending_step, pending_step
 from ._linear import _LinearLauncher
+from .softmax import plan_softmax
 from ._operands import FAMILY_CODES, _INTEGER_VALUED, _View, _collapse, _float, _to_device
 
 
@@ -38,7 +39,8 @@ def claim_linear_draws(trace: ParticleTrace) -> Dict[int, guide.PendingDraw]:
     thetas: Dict[guide.PendingDraw, list] = collections.defaultdict(list)
     others: Dict[guide.PendingDraw, list] = collections.defaultdict(list)
     for site in trace.sites:
-        if site.linear_X is not None and site.linear_theta is not None:
+        if site.linear_X is not None and site.linear_theta is not None and \
+                site.family != "categorical":   # (the softmax site's kernel does not draw)
             rec = guide.pending_draw(site.linear_theta)
             if rec is not None:
                 thetas[rec].append(site)
@@ -145,8 +147,8 @@ def plan_linear(trace: ParticleTrace, g0: float, device: torch.device,
     K = trace.K
     out: List[_LinearLauncher] = []
     for site in trace.sites:
-        if site.linear_X is None:
-            continue
+        if site.linear_X is None or site.family == "categorical":
+            continue   # (a Categorical on X @ Theta: plan_groups, through plan_softmax)
         theta = site.linear_theta
         shape = site.site_shape
         launcher = None
@@ -304,6 +306,11 @@ def plan_groups(trace: ParticleTrace, g0: float, device: torch.device):
     groups: List[Tuple[torch.Size, _GroupLauncher]] = []
     categorical = []
     for site in trace.sites:
+        if site.linear_X is not None and site.family == "categorical":
+            entry = plan_softmax(site, K, device)   # (None: materialised, the row site below)
+            if entry is not None:
+                categorical.append(entry)
+                continue
         if site.linear_X is not None:
             continue   # planned by plan_linear
         if site.family == "categorical":

@@ -186,6 +186,9 @@ def _run_row_site(site: SiteRecord, g0: float, params: Tuple[torch.Tensor, ...],
                                    (*[p.requires_grad for p in params], value.requires_grad),
                                    flags)
     param, = params
+    if site.linear_X is not None:   # a Categorical on a deferred X @ Theta (engine.softmax)
+        total, dtheta, flags = site.softmax.run(param, g0, param.requires_grad, flags)
+        return total, (dtheta,), None, flags
     if site.family == "dirichlet":
         total, dconc, dvalue, flags = _run_dirichlet(
             site, g0, param, value, mask, (param.requires_grad, value.requires_grad), flags)
@@ -197,5 +200,8 @@ def _run_row_site(site: SiteRecord, g0: float, params: Tuple[torch.Tensor, ...],
 
 def row_site_fn(site: SiteRecord):
     """The autograd function of a row site evaluated on its own (engine.log_joint)."""
+    if site.linear_X is not None:
+        from .softmax import _SoftmaxLinearFn
+        return _SoftmaxLinearFn
     return {"dirichlet": _DirichletFn, "mixture_normal": _MixtureNormalFn}.get(site.family,
                                                                             _CategoricalFn)

@@ -14,6 +14,16 @@ whose ``rate`` is ``exp`` of one -- ``torch.exp`` / ``Tensor.exp`` of a placehol
 tagged with the *link* ``exp`` (the log link of the regression), which materialises to ``exp`` of
 the real product.
 
+The multi-class regression ``Categorical(logits=X @ Theta)`` with a per-particle matrix ``Theta``
+[P, C] is deferred the same way (``torch.matmul`` only; the placeholder has shape [N, C]).
+``Categorical.__init__`` normalises its logits, ``logits - logits.logsumexp(dim=-1, keepdim=True)``:
+``logsumexp`` of such a placeholder over its last dimension (``keepdim=True``) is a placeholder
+[N, 1] with the link ``logsumexp``, the difference of the two (and ``log_softmax`` over the last
+dimension) one with the link ``log_softmax``; a ``log_softmax`` placeholder normalises again the
+same way (``Categorical(logits=torch.log_softmax(eta, -1))``). The tracer turns a Categorical site whose logits are
+an identity or ``log_softmax`` placeholder into a fused softmax site
+(``mi_softmax_linear_forward``).
+
 Semantics are preserved for every other use: any torch operation that reads a placeholder's values
 (anything but shape queries and broadcasting views) first *materialises* it -- the real
 ``torch.matmul(X, theta)`` is computed at that point, exactly as the model wrote it -- and the
@@ -34,6 +44,7 @@ from .guide import lazy_of
 _functorch = torch._C._functorch
 
 _MATMULS = {torch.matmul, torch.Tensor.matmul, torch.Tensor.__matmul__, torch.mv, torch.Tensor.mv}
+_MVS = {torch.mv, torch.Tensor.mv}
 
 # Operations that only read metadata (never values) pass a placeholder through unchanged.
 _METADATA = {
@@ -48,6 +59,14 @@ _METADATA = {
 
 # exp of an identity-link placeholder is a placeholder with the link "exp" (Poisson's log link).
 _EXPS = {torch.exp, torch.Tensor.exp}
+
+# The normalisation of Categorical's logits over a [N, C] placeholder (see the module docstring).
+_LOGSUMEXPS = {torch.logsumexp, torch.Tensor.logsumexp}
+_SUBS = {torch.sub, torch.Tensor.sub, torch.Tensor.__sub__}
+_LOG_SOFTMAXES = {torch.log_softmax, torch.Tensor.log_softmax, torch.nn.functional.log_softmax}
+
+# Most categories of a deferred `X @ Theta` (MI_SOFTMAX_LINEAR_MAX_C of include/mininf_amd.h).
+MAX_CATEGORIES = 32
 
 # Broadcasting views of a placeholder are placeholders of the broadcast shape (and the same link).
 _BROADCASTS = {torch.broadcast_tensors, torch.Tensor.expand, torch.Tensor.expand_as,
@@ -80,7 +99,8 @@ class Deferred:
     """
     ``root``: the deferred ``X @ theta`` (``X`` [N, P] observed, ``theta`` batched [P]); a derived
     placeholder is ``root`` broadcast to ``shape``, then passed through ``link`` ("identity" or
-    "exp").
+    "exp"). With ``theta`` batched [P, C] the root has shape [N, C], and the links "logsumexp"
+    (over the last dimension, kept) and "log_softmax" are applied before the broadcast.
     """
     X: torch.Tensor
     theta: torch.Tensor
@@ -88,6 +108,10 @@ class Deferred:
     root: Optional["Deferred"] = None
     real: Optional[torch.Tensor] = None
     link: str = "identity"
+    # the normalisations behind a "log_softmax" placeholder (or under a "logsumexp" one), in order:
+    # "sub" (x - x.logsumexp(-1, keepdim=True), as Categorical.__init__ writes it) or "log_softmax";
+    # Categorical(logits=torch.log_softmax(eta, -1)) normalises twice
+    steps: Tuple[str, ...] = ()
 
 
 class DeferredMatmul(TorchFunctionMode):
@@ -110,7 +134,8 @@ class DeferredMatmul(TorchFunctionMode):
             return self.deferred.get(id(tensor))
         return None
 
-    def _eligible(self, args, kwargs) -> bool:
+    def _eligible(self, args, kwargs, matrix: bool = False) -> bool:
+        """``matrix``: the call is a matmul (not ``mv``), which also takes a [P, C] theta."""
         if kwargs or len(args) != 2:
             return False
         X, theta = args
@@ -123,7 +148,9 @@ class DeferredMatmul(TorchFunctionMode):
         return (not _functorch.is_batchedtensor(X) and X.dim() == 2 and
                 (X.is_cuda or not self.require_device) and
                 X.dtype == torch.float32 and not X.requires_grad and
-                _functorch.is_batchedtensor(theta) and theta.dim() == 1 and
+                _functorch.is_batchedtensor(theta) and
+                (theta.dim() == 1 or (matrix and theta.dim() == 2 and
+                                      2 <= theta.shape[1] <= MAX_CATEGORIES)) and
                 theta.dtype == torch.float32 and theta.shape[0] == X.shape[1] and
                 X.shape[1] <= 64 and X.shape[0] > 0)
 
@@ -157,9 +184,18 @@ class DeferredMatmul(TorchFunctionMode):
         if info.real is None:
             self._bypass = True
             try:
-                info.real = root.real.expand(info.shape)
-                if info.link == "exp":
-                    info.real = info.real.exp()
+                if info.link in ("logsumexp", "log_softmax"):
+                    real = root.real
+                    for step in info.steps:   # each as the model wrote it
+                        real = torch.log_softmax(real, -1) if step == "log_softmax" else \
+                            real - real.logsumexp(dim=-1, keepdim=True)
+                    if info.link == "logsumexp":
+                        real = real.logsumexp(dim=-1, keepdim=True)
+                    info.real = real.expand(info.shape)
+                else:
+                    info.real = root.real.expand(info.shape)
+                    if info.link == "exp":
+                        info.real = info.real.exp()
             finally:
                 self._bypass = False
         return info.real
@@ -169,9 +205,9 @@ class DeferredMatmul(TorchFunctionMode):
         kwargs = kwargs or {}
         if self._bypass:
             return func(*args, **kwargs)
-        if func in _MATMULS and self._eligible(args, kwargs):
+        if func in _MATMULS and self._eligible(args, kwargs, func not in _MVS):
             X, theta = args
-            info = Deferred(X=X, theta=theta, shape=torch.Size([X.shape[0]]))
+            info = Deferred(X=X, theta=theta, shape=torch.Size((X.shape[0],) + tuple(theta.shape[1:])))
             return self._placeholder(theta, info.shape, info)
         if not self.deferred and not _guide._LAZY and \
                 (not _guide._PENDING_DRAWS or func in _METADATA or func in _BROADCASTS):
@@ -219,9 +255,46 @@ class DeferredMatmul(TorchFunctionMode):
             derived = Deferred(X=root.X, theta=root.theta, shape=torch.Size(args[0].shape),
                                root=root, link="exp")
             return self._placeholder(args[0], derived.shape, derived)
+        derived = self._softmax_link(func, args, kwargs)
+        if derived is not None:
+            return self._placeholder(args[0], derived.shape, derived)
         args, kwargs = tree_map(lambda x: self.materialize(x) if self.lookup(x) else x,
                                 (args, kwargs))
         return func(*args, **kwargs)
+
+    def _softmax_link(self, func: Callable, args, kwargs) -> Optional[Deferred]:
+        """
+        The derived placeholder of ``logsumexp(ph, -1, keepdim=True)``, ``ph - lse`` or
+        ``log_softmax(ph, -1)`` over a [.., N, C] identity placeholder ``ph``; None for anything else.
+        """
+        info = self.lookup(args[0]) if args else None
+        if info is None or info.link not in ("identity", "log_softmax") or \
+                (info.root or info).theta.dim() != 2:
+            return None
+        root = info.root or info
+        shape = tuple(args[0].shape)
+
+        def last_dim(extra) -> bool:
+            rest = dict(kwargs)
+            rest.pop("_stacklevel", None)
+            dim = args[1] if len(args) > 1 else rest.pop("dim", None)
+            if len(args) > 2 or isinstance(dim, bool) or not isinstance(dim, int):
+                return False
+            return dim in (-1, len(shape) - 1) and rest == extra
+
+        if func in _LOGSUMEXPS and last_dim({"keepdim": True}):
+            return Deferred(X=root.X, theta=root.theta, shape=torch.Size(shape[:-1] + (1,)),
+                            root=root, link="logsumexp", steps=info.steps)
+        if func in _LOG_SOFTMAXES and (last_dim({}) or last_dim({"dtype": None})):
+            return Deferred(X=root.X, theta=root.theta, shape=torch.Size(shape), root=root,
+                            link="log_softmax", steps=info.steps + ("log_softmax",))
+        if func in _SUBS and len(args) == 2 and not kwargs:
+            other = self.lookup(args[1])
+            if other is not None and other.link == "logsumexp" and other.root is root and \
+                    other.steps == info.steps and tuple(args[1].shape) == shape[:-1] + (1,):
+                return Deferred(X=root.X, theta=root.theta, shape=torch.Size(shape), root=root,
+                                link="log_softmax", steps=info.steps + ("sub",))
+        return None
 
     def _derive(self, src: Any, dst: torch.Tensor) -> None:
         info = self.lookup(src)
@@ -229,5 +302,6 @@ class DeferredMatmul(TorchFunctionMode):
             return
         root = info.root or info
         self.deferred[id(dst)] = Deferred(X=root.X, theta=root.theta,
-                                          shape=torch.Size(dst.shape), root=root, link=info.link)
+                                          shape=torch.Size(dst.shape), root=root, link=info.link,
+                                          steps=info.steps)
         self._keep.append(dst)

@@ -115,7 +115,9 @@ class SiteRecord:
     linear_theta_index: int = -1
     linear_theta: Optional[torch.Tensor] = None
     linear_role: int = 0      # the role that is the deferred predictor (Binomial families: 1)
-    linear_link: str = ""     # "identity", or "exp" (a Poisson rate: the log link)
+    softmax: Any = None       # engine: the mi_softmax_linear launcher of a Categorical on X @ Theta
+    linear_link: str = ""     # "identity", "exp" (a Poisson rate: the log link) or, for a
+                              # Categorical's logits over a [P, C] theta, "log_softmax"
     order: int = 0   # position of the sample statement in the model (errors raise in this order)
     extra: float = 0.0   # the family's constant fourth input (mi_site.extra): StudentT's df
 
@@ -581,7 +583,17 @@ class ParticleTracer(TracerMixin):
             else:
                 eligible = family in ("normal", "bernoulli_logits", "poisson")
             info = mode.lookup(params[role]) if params else None
-            if info is not None and eligible and \
+            if family == "categorical":
+                # Categorical(logits=X @ Theta), Theta [P, C] per particle: the softmax site
+                # normalises either way, so the raw product and its log_softmax are both taken
+                if info is not None and "logits" in distribution.__dict__ and \
+                        info.link in ("identity", "log_softmax") and \
+                        (info.root or info).theta.dim() == 2 and not is_batched(data) and \
+                        tuple(shape) == (info.X.shape[0],) and tuple(data.shape) == tuple(shape) and \
+                        tuple(info.shape) == tuple(shape) + (info.theta.shape[1],):
+                    linear = info.root or info
+                    link = info.link
+            elif info is not None and eligible and info.theta.dim() == 1 and \
                     info.link == ("exp" if family == "poisson" else "identity") and \
                     not is_batched(data) and tuple(shape) == (info.X.shape[0],) and \
                     tuple(data.shape) == tuple(shape) and \
