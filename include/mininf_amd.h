@@ -988,6 +988,115 @@ int mi_softmax_linear_forward(const mi_softmax_linear* site, void* workspace,
                               float* dtheta /* [K, P, C] contiguous or NULL */, uint32_t* flags,
                               void* stream);
 
+/* ---- group-indexed sites (a parameter indexed by a group label: alpha[group]) -------------------- */
+
+/* A Normal, Bernoulli-logits or Poisson site over N rows of shared data whose parameter is the
+ * model's own gather table[index] of a per-particle table [K, G] (a random intercept per group).
+ * The gather is evaluated inside the site kernel, so neither the [K, N] parameter nor its [K, N]
+ * gradient exists in memory, and the gradient reaches the table without atomics. The site has two
+ * parameter roles (Normal: loc, scale; Bernoulli: logits, -; Poisson: rate, -), each one of
+ *   MI_GATHER_GATHER    p[k, g_i] = data[k * stride_k + g_i * stride_g], g_i the row's group
+ *   MI_GATHER_PARTICLE  data[k * stride_k]
+ *   MI_GATHER_DATA      data[i * stride_g]
+ *   MI_GATHER_CONSTANT  constant
+ * and at least one a GATHER (both may be: they share the index, not the table). A GATHER role is
+ * the link of an affine predictor: eta = shift_k + mult_k * p[k, g_i] (shift and mult each absent,
+ * one float per particle or a constant), role = eta (MI_GATHER_LINK_IDENTITY) or exp(eta)
+ * (MI_GATHER_LINK_EXP). A Poisson site's rate is a GATHER role with the exp link (the log link of
+ * the regression: log p = y eta - exp(eta) - lgamma(y + 1)); anything else is MI_EUNSUPPORTED.
+ *
+ * The index arrives sorted: order[j] is a permutation of the rows, stable-sorted by group, and
+ * sorted_group[j] = index[order[j]] (both int32 [N]); value, mask and DATA roles are read at row
+ * order[j]. sorted_group must be non-decreasing over all its entries (the launch finds a group's
+ * rows by binary search): with an unsorted array no address leaves the buffers, but the sums are
+ * undefined. An entry of sorted_group outside [0, G) (or of order outside [0, N)) contributes
+ * nothing, is never used as an address and sets MI_FLAG_INTERNAL.
+ *   total[k]     = site_scale * sum_i mask_i * log p_i
+ *   dtable[k, g] = g0 * site_scale * mult_k * sum_{i: g_i = g} mask_i * d log p_i / d eta
+ *                  (grads->role[r] of a GATHER role: contiguous [K, G], every entry written, 0 for
+ *                  a group without rows)
+ *   grads->role[r] of a PARTICLE role, grads->shift[r], grads->mult[r]: [K], the sums over rows of
+ *                  g0 * site_scale * mask_i * d log p_i / d (role | shift | mult)
+ * grads, or any pointer in it, may be NULL (not written; those of DATA and CONSTANT roles and of
+ * shifts and mults that are not per particle are ignored). flags[0] (zeroed by the call unless
+ * options has MI_GROUP_FLAGS_ZEROED): MI_FLAG_SUPPORT for an observed value outside the family's
+ * support, MI_FLAG_PARAM for a non-finite eta, a NaN loc or logits or a scale that is not positive
+ * on an observed row; a masked-out row adds nothing and sets no flag.
+ *
+ * A wave's lane takes one particle and walks MI_GATHER_ROWS consecutive sorted rows (a chunk): the
+ * rows of a group are consecutive, so its sum stays in a register and is stored once. A group that
+ * continues in the neighbouring chunk leaves its part in the workspace ([chunks, K] per role and
+ * chunk end); a finishing launch of the same call adds those in chunk order, writes the zeros of
+ * the empty groups and sums the chunks' values. No floating-point atomics: two calls on the same
+ * inputs give the same bits.
+ * MI_EINVAL: a NULL site, order, sorted_group, value, total or flags; K, N or G < 1; an unknown
+ * family, kind, link, shift_kind, mult_kind or value_kind; no GATHER role; a GATHER, PARTICLE or
+ * DATA role without data; a per-particle shift or mult without its pointer. MI_EWORKSPACE: a
+ * workspace smaller than mi_gather_site_workspace_bytes asks for. All checked before any device
+ * work. */
+#define MI_GATHER_CONSTANT 0
+#define MI_GATHER_GATHER 1
+#define MI_GATHER_PARTICLE 2
+#define MI_GATHER_DATA 3
+#define MI_GATHER_LINK_IDENTITY 0
+#define MI_GATHER_LINK_EXP 1
+#define MI_GATHER_TERM_NONE 0      /* shift = 0, mult = 1 */
+#define MI_GATHER_TERM_PARTICLE 1
+#define MI_GATHER_TERM_CONSTANT 2
+#define MI_GATHER_VALUE_FLOAT32 0
+#define MI_GATHER_VALUE_INT64 1
+#define MI_GATHER_ROWS 256         /* sorted rows of a chunk */
+
+typedef struct mi_gather_role {
+  int32_t kind;           /* MI_GATHER_CONSTANT | GATHER | PARTICLE | DATA */
+  int32_t link;           /* MI_GATHER_LINK_* (GATHER roles) */
+  const float* data;
+  int64_t stride_k;       /* GATHER, PARTICLE: between particles */
+  int64_t stride_g;       /* GATHER: between groups; DATA: between rows */
+  float constant;
+  int32_t shift_kind;     /* MI_GATHER_TERM_* (GATHER roles) */
+  int32_t mult_kind;
+  float shift_constant;
+  float mult_constant;
+  int32_t pad0;
+  const float* shift;     /* shift[k * shift_stride_k] */
+  int64_t shift_stride_k;
+  const float* mult;
+  int64_t mult_stride_k;
+} mi_gather_role;
+
+typedef struct mi_gather_site {
+  int64_t K;
+  int64_t N;
+  int64_t G;
+  int32_t family;         /* MI_NORMAL, MI_BERNOULLI_LOGITS or MI_POISSON */
+  int32_t options;        /* MI_GROUP_FLAGS_ZEROED */
+  mi_gather_role role[2];
+  const int32_t* order;         /* [N] */
+  const int32_t* sorted_group;  /* [N] */
+  const void* value;      /* float32 or int64 (value_kind) at value[i * value_stride_i] */
+  int64_t value_stride_i;
+  int32_t value_kind;     /* MI_GATHER_VALUE_* */
+  int32_t pad0;
+  const uint8_t* mask;    /* NULL or mask[i * mask_stride_i] */
+  int64_t mask_stride_i;
+  double site_scale;      /* minibatch scale (core.py:267-271) */
+  float grad_scale;       /* g0 */
+  int32_t pad1;
+} mi_gather_site;
+
+typedef struct mi_gather_grads {
+  float* role[2];
+  float* shift[2];
+  float* mult[2];
+} mi_gather_grads;
+
+int mi_gather_site_struct_size(size_t* bytes);
+int mi_gather_site_workspace_bytes(const mi_gather_site* site, size_t* bytes);
+int mi_gather_site_forward(const mi_gather_site* site, void* workspace, size_t workspace_bytes,
+                           float* total /* [K] */, const mi_gather_grads* grads /* or NULL */,
+                           uint32_t* flags, void* stream);
+
 /* ---- device-resident minibatches (replaces examples/minibatch.md:78-88, the host DataLoader) ---- */
 
 /* Row indices of the next minibatch of an n-row dataset: with c = counter[0] (then counter[0] =

@@ -155,6 +155,48 @@ class SoftmaxLinear(ctypes.Structure):
     ]
 
 
+# mi_gather_role.kind, .link, .shift_kind / .mult_kind and mi_gather_site.value_kind
+GATHER_CONSTANT, GATHER_GATHER, GATHER_PARTICLE, GATHER_DATA = 0, 1, 2, 3
+GATHER_LINK_IDENTITY, GATHER_LINK_EXP = 0, 1
+GATHER_TERM_NONE, GATHER_TERM_PARTICLE, GATHER_TERM_CONSTANT = 0, 1, 2
+GATHER_VALUE_FLOAT32, GATHER_VALUE_INT64 = 0, 1
+GATHER_ROWS = 256   # MI_GATHER_ROWS
+
+
+class GatherRole(ctypes.Structure):
+    """mi_gather_role (include/mininf_amd.h)."""
+    _fields_ = [
+        ("kind", ctypes.c_int32), ("link", ctypes.c_int32),
+        ("data", c_vp), ("stride_k", c_i64), ("stride_g", c_i64),
+        ("constant", ctypes.c_float),
+        ("shift_kind", ctypes.c_int32), ("mult_kind", ctypes.c_int32),
+        ("shift_constant", ctypes.c_float), ("mult_constant", ctypes.c_float),
+        ("pad0", ctypes.c_int32),
+        ("shift", c_vp), ("shift_stride_k", c_i64),
+        ("mult", c_vp), ("mult_stride_k", c_i64),
+    ]
+
+
+class GatherSite(ctypes.Structure):
+    """mi_gather_site (include/mininf_amd.h)."""
+    _fields_ = [
+        ("K", c_i64), ("N", c_i64), ("G", c_i64),
+        ("family", ctypes.c_int32), ("options", ctypes.c_int32),
+        ("role", GatherRole * 2),
+        ("order", c_vp), ("sorted_group", c_vp),
+        ("value", c_vp), ("value_stride_i", c_i64),
+        ("value_kind", ctypes.c_int32), ("pad0", ctypes.c_int32),
+        ("mask", c_vp), ("mask_stride_i", c_i64),
+        ("site_scale", ctypes.c_double),
+        ("grad_scale", ctypes.c_float), ("pad1", ctypes.c_int32),
+    ]
+
+
+class GatherGrads(ctypes.Structure):
+    """mi_gather_grads (include/mininf_amd.h)."""
+    _fields_ = [("role", c_vp * 2), ("shift", c_vp * 2), ("mult", c_vp * 2)]
+
+
 class Source(ctypes.Structure):
     _fields_ = [("ptr", c_vp), ("stride_k", c_i64), ("stride_i", c_i64)]
 
@@ -403,6 +445,11 @@ _SIGNATURES = {
                                                          ctypes.POINTER(ctypes.c_size_t)]),
     "mi_softmax_linear_forward": (ctypes.c_int, [ctypes.POINTER(SoftmaxLinear), c_vp,
                                                  ctypes.c_size_t, c_vp, c_vp, c_vp, c_vp]),
+    "mi_gather_site_struct_size": (ctypes.c_int, [ctypes.POINTER(ctypes.c_size_t)]),
+    "mi_gather_site_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(GatherSite),
+                                                      ctypes.POINTER(ctypes.c_size_t)]),
+    "mi_gather_site_forward": (ctypes.c_int, [ctypes.POINTER(GatherSite), c_vp, ctypes.c_size_t,
+                                              c_vp, ctypes.POINTER(GatherGrads), c_vp, c_vp]),
     "mi_minibatch_rows": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, ctypes.c_int32,
                                          ctypes.c_uint64, c_vp, c_i64, c_vp]),
     "mi_gather_rows": (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
@@ -472,6 +519,12 @@ def lib() -> ctypes.CDLL:
         if softmax.value != ctypes.sizeof(SoftmaxLinear):
             raise NativeError(f"{LIB_PATH} lays mi_softmax_linear out in {softmax.value} bytes, this "
                               f"binding in {ctypes.sizeof(SoftmaxLinear)}; rebuild it "
+                              "(mininf_amd/build.py --force).")
+        gather = ctypes.c_size_t()
+        handle.mi_gather_site_struct_size(ctypes.byref(gather))
+        if gather.value != ctypes.sizeof(GatherSite):
+            raise NativeError(f"{LIB_PATH} lays mi_gather_site out in {gather.value} bytes, this "
+                              f"binding in {ctypes.sizeof(GatherSite)}; rebuild it "
                               "(mininf_amd/build.py --force).")
         _LIB = handle
     return _LIB

@@ -119,7 +119,7 @@ def _lazy_uses(trace: ParticleTrace) -> Tuple[set, set]:
             if lazy is None:
                 continue
             seen.add(lazy)
-            if site.linear_X is not None or \
+            if site.linear_X is not None or site.gather_roles is not None or \
                     site.family in ("categorical", "dirichlet", "mixture_normal") or \
                     tuple(t.shape[1:]) != tuple(site.site_shape) or \
                     int(site.site_shape.numel()) != lazy.N:

@@ -430,7 +430,8 @@ class _ElboPlan:
         HalfNormal and LogNormal guide factors drawn by the native sampler
         (mi_elementwise_rsample); lowrank_entropies: LowRankMultivariateNormal guide factors whose
         entropy and its gradient the native kernel evaluated (mi_lowrank_entropy, called by the
-        loss after this plan ran).
+        loss after this plan ran); gathered_sites: sites on the model's own ``alpha[group]`` that
+        this evaluation ran on mi_gather_site_forward (no [K, N] gather, no scatter-add).
         """
         return {
             "folded_priors": sum(l.prior is not None for l in self.launchers) +
@@ -448,6 +449,8 @@ class _ElboPlan:
             "lowrank_draws": guide.lowrank_draws(),
             "elementwise_draws": guide.elementwise_draws(),
             "lowrank_entropies": 0,   # set by the loss, which evaluates the rest's entropies
+            "gathered_sites": sum(site.gather is not None and site.gather.launches > 0
+                                  for site, _, _, _ in self.categorical),
         }
 
     def _reduce_ok(self, assume=None) -> bool:

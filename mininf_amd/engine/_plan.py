@@ -19,6 +19,7 @@ from ._groups import _QUERY_ADDRESS, _GroupLauncher
 from ._held import flush_pending_step, pending_step
 from ._linear import _LinearLauncher
 from .softmax import plan_softmax
+from .gather import plan_gather
 from ._operands import FAMILY_CODES, _INTEGER_VALUED, _View, _collapse, _float, _to_device
 
 
@@ -300,12 +301,18 @@ def plan_groups(trace: ParticleTrace, g0: float, device: torch.device):
     """
     Prepare every recorded site for launch: categorical, Dirichlet and mixture sites as (site,
     parameters, value, mask) with the parameters a tuple of [K, N, C] tensors (logits |
-    concentration | logits, loc, scale) and the other families packed into site groups sharing their element space and a dense operand.
+    concentration | logits, loc, scale), sites on a deferred ``alpha[group]`` the same way with
+    their tables and per-particle terms (engine.gather), and the other families packed into site groups sharing their element space and a dense operand.
     """
     K = trace.K
     groups: List[Tuple[torch.Size, _GroupLauncher]] = []
     categorical = []
     for site in trace.sites:
+        if site.gather_roles is not None:
+            entry = plan_gather(site, K, device)   # (None: materialised, grouped below)
+            if entry is not None:
+                categorical.append(entry)
+                continue
         if site.linear_X is not None and site.family == "categorical":
             entry = plan_softmax(site, K, device)   # (None: materialised, the row site below)
             if entry is not None:

@@ -179,8 +179,11 @@ class _MixtureNormalFn(torch.autograd.Function):
 def _run_row_site(site: SiteRecord, g0: float, params: Tuple[torch.Tensor, ...],
                   value: torch.Tensor, mask: Optional[torch.Tensor],
                   flags: Optional[torch.Tensor] = None):
-    """A categorical, Dirichlet or mixture site's launch: (total, the parameters' gradients as a
-    tuple, dvalue, flags)."""
+    """A categorical, Dirichlet, mixture or gathered site's launch: (total, the parameters'
+    gradients as a tuple, dvalue, flags)."""
+    if site.gather is not None:   # a site on a deferred alpha[group] (engine.gather)
+        total, grads, flags = site.gather.run(params, g0, flags)
+        return total, grads, None, flags
     if site.family == "mixture_normal":
         return _run_mixture_normal(site, g0, params, value, mask,
                                    (*[p.requires_grad for p in params], value.requires_grad),
@@ -200,6 +203,9 @@ def _run_row_site(site: SiteRecord, g0: float, params: Tuple[torch.Tensor, ...],
 
 def row_site_fn(site: SiteRecord):
     """The autograd function of a row site evaluated on its own (engine.log_joint)."""
+    if site.gather is not None:
+        from .gather import _GatherSiteFn
+        return _GatherSiteFn
     if site.linear_X is not None:
         from .softmax import _SoftmaxLinearFn
         return _SoftmaxLinearFn

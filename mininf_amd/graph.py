@@ -165,6 +165,8 @@ def _release_graph_refs(joints: list) -> None:
                 site.tensors = []
                 site.linear_theta = None
                 site.linear_X = None
+                site.gather_roles = None
+                site.gather = None
 
 
 def _check_warmup(collector: list) -> int:

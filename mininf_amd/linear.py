@@ -24,6 +24,15 @@ same way (``Categorical(logits=torch.log_softmax(eta, -1))``). The tracer turns 
 an identity or ``log_softmax`` placeholder into a fused softmax site
 (``mi_softmax_linear_forward``).
 
+A parameter indexed by a group label, ``alpha[group]`` with a per-particle table ``alpha`` [G] and
+an observed 1-D integer ``group`` [N] (``Tensor.__getitem__`` or ``index_select`` over dimension
+0), is deferred the same way (:class:`DeferredGather`): the placeholder [N] stays one through
+broadcasting views, through ``add`` / ``sub`` / ``mul`` (and their reflected forms) with a Python
+number or a per-particle scalar -- they compose the affine predictor ``shift + mult * alpha[group]``
+-- and through ``exp`` of it. The tracer turns a Normal / Bernoulli-logits / Poisson site whose
+parameter is such a placeholder into a gathered site (``mi_gather_site_forward``: the [K, N] gather
+and its scatter-add backward never run). ``MININF_AMD_DEFER_GATHER=0`` turns this off.
+
 Semantics are preserved for every other use: any torch operation that reads a placeholder's values
 (anything but shape queries and broadcasting views) first *materialises* it -- the real
 ``torch.matmul(X, theta)`` is computed at that point, exactly as the model wrote it -- and the
@@ -39,6 +48,7 @@ from torch.overrides import TorchFunctionMode
 from torch.utils._pytree import tree_map
 
 from . import guide as _guide
+from . import switches
 from .guide import lazy_of
 
 _functorch = torch._C._functorch
@@ -71,6 +81,17 @@ MAX_CATEGORIES = 32
 # Broadcasting views of a placeholder are placeholders of the broadcast shape (and the same link).
 _BROADCASTS = {torch.broadcast_tensors, torch.Tensor.expand, torch.Tensor.expand_as,
                torch.Tensor.broadcast_to, torch.broadcast_to}
+
+
+# A gather `table[index]` over dimension 0, and the arithmetic that keeps its placeholder one.
+_GETITEMS = {torch.Tensor.__getitem__}
+_INDEX_SELECTS = {torch.index_select, torch.Tensor.index_select}
+_ADDS = {torch.add: False, torch.Tensor.add: False, torch.Tensor.__add__: False,
+         torch.Tensor.__radd__: True}
+_MULS = {torch.mul: False, torch.Tensor.mul: False, torch.Tensor.__mul__: False,
+         torch.Tensor.__rmul__: True}
+_SUBTRACTS = {torch.sub: False, torch.Tensor.sub: False, torch.Tensor.__sub__: False,
+              torch.Tensor.__rsub__: True}   # True: reflected, func(x, y) = y op x
 
 
 class NeedsDraws(Exception):
@@ -114,17 +135,47 @@ class Deferred:
     steps: Tuple[str, ...] = ()
 
 
+@dataclasses.dataclass
+class DeferredGather:
+    """
+    A placeholder of ``link(shift + mult * table[index])`` broadcast to ``shape``: ``table`` batched
+    [G], ``index`` an observed 1-D integer tensor [N], ``shift`` / ``mult`` None (0 / 1), a Python
+    number or a per-particle (batched 0-d) tensor, ``link`` "identity" or "exp". ``parent`` and
+    ``replay`` materialise it: the parent's real value passed through the operation as the model
+    wrote it (the root: the gather itself). ``chain`` lists those operations, in order, for a
+    planner that has to put the gather back after the trace: ("add" | "sub" | "mul", c, left) with
+    the placeholder the left operand or not.
+    """
+    table: torch.Tensor
+    index: torch.Tensor
+    shape: torch.Size
+    shift: Any = None
+    mult: Any = None
+    link: str = "identity"
+    parent: Optional["DeferredGather"] = None
+    replay: Optional[Callable] = None
+    real: Optional[torch.Tensor] = None
+    chain: Tuple[Tuple[str, Any, bool], ...] = ()
+
+
 class DeferredMatmul(TorchFunctionMode):
     """
     Active while a model is traced over particles (inside ``vmap``); see the module docstring.
     """
     require_device = True   # defer only device matmuls (the fused kernel's operands)
 
-    def __init__(self, K: int, defer_matmul: bool = True) -> None:
+    def __init__(self, K: int, defer_matmul: bool = True,
+                 defer_gather: Optional[bool] = None) -> None:
         super().__init__()
         self.K = K
         self.defer_matmul = defer_matmul
+        self.defer_gather = switches.enabled("DEFER_GATHER") if defer_gather is None \
+            else defer_gather
         self.deferred: Dict[int, Deferred] = {}
+        self.gathers: Dict[int, DeferredGather] = {}
+        # per-particle scalars broadcast beside a gather placeholder (Normal's broadcast_all of
+        # loc and scale): the broadcast view -> the scalar it came from
+        self.sources: Dict[int, torch.Tensor] = {}
         self._keep: List[torch.Tensor] = []   # placeholders stay alive: ids are never reused
         self._bypass = False
 
@@ -133,6 +184,117 @@ class DeferredMatmul(TorchFunctionMode):
         if isinstance(tensor, torch.Tensor):
             return self.deferred.get(id(tensor))
         return None
+
+    def lookup_gather(self, tensor: Any) -> Optional[DeferredGather]:
+        if isinstance(tensor, torch.Tensor):
+            return self.gathers.get(id(tensor))
+        return None
+
+    def _gather_call(self, func: Callable, args, kwargs):
+        """(table, index) of a call that is ``table[index]`` over a per-particle 1-D float32
+        table and an observed 1-D integer index, or None."""
+        if func in _GETITEMS:
+            if kwargs or len(args) != 2:
+                return None
+            table, index = args
+        elif func in _INDEX_SELECTS:
+            names = ("input", "dim", "index")
+            if len(args) > 3 or any(key not in names[len(args):] for key in kwargs):
+                return None
+            full = list(args) + [kwargs.get(name) for name in names[len(args):]]
+            table, dim, index = full
+            if isinstance(dim, bool) or not isinstance(dim, int) or dim not in (0, -1):
+                return None
+        else:
+            return None
+        if not (isinstance(table, torch.Tensor) and isinstance(index, torch.Tensor)):
+            return None
+        if self.lookup(table) is not None or self.lookup_gather(table) is not None or \
+                lazy_of(table) is not None or lazy_of(index) is not None:
+            return None
+        if not (_functorch.is_batchedtensor(table) and table.dim() == 1 and
+                table.dtype == torch.float32 and table.shape[0] > 0 and
+                (table.is_cuda or not self.require_device)):
+            return None
+        if _functorch.is_batchedtensor(index) or index.dim() != 1 or index.shape[0] == 0 or \
+                index.dtype not in (torch.int64, torch.int32) or index.requires_grad or \
+                index.device != table.device:
+            return None
+        return table, index
+
+    def _gather_placeholder(self, like: torch.Tensor, info: DeferredGather) -> torch.Tensor:
+        level = _functorch.maybe_get_level(like)
+        base = torch.empty((), dtype=torch.float32, device=info.table.device)
+        base = base.expand((self.K,) + tuple(info.shape))
+        out = _functorch._add_batch_dim(base, 0, level)
+        self.gathers[id(out)] = info
+        self._keep.append(out)
+        return out
+
+    def _scalar(self, x: Any) -> bool:
+        """A Python number or a per-particle float32 scalar: a term of the affine predictor."""
+        if isinstance(x, bool):
+            return False
+        if isinstance(x, (int, float)):
+            return True
+        return isinstance(x, torch.Tensor) and _functorch.is_batchedtensor(x) and x.dim() == 0 and \
+            x.dtype == torch.float32 and self.lookup(x) is None and \
+            self.lookup_gather(x) is None and lazy_of(x) is None
+
+    def _affine(self, func: Callable, args, kwargs) -> Optional[torch.Tensor]:
+        """The placeholder of ``ph + c``, ``ph - c``, ``c - ph`` or ``ph * c`` for an identity-link
+        gather placeholder ``ph`` and a scalar ``c``; None for anything else."""
+        kind = "add" if func in _ADDS else "mul" if func in _MULS else \
+            "sub" if func in _SUBTRACTS else None
+        if kind is None or kwargs or len(args) != 2:
+            return None
+        reflected = (_ADDS if kind == "add" else _MULS if kind == "mul" else _SUBTRACTS)[func]
+        x, y = (args[1], args[0]) if reflected else args   # the call computes x op y
+        if self.lookup_gather(x) is not None and self._scalar(y):
+            ph, c, left = x, y, True
+        elif self.lookup_gather(y) is not None and self._scalar(x):
+            ph, c, left = y, x, False
+        else:
+            return None
+        info = self.lookup_gather(ph)
+        if info.link != "identity":
+            return None
+        shift, mult = info.shift, info.mult
+        self._bypass = True   # (per-particle scalars: [K] operations)
+        try:
+            if kind == "add":
+                shift = c if shift is None else shift + c
+            elif kind == "sub" and left:
+                shift = -c if shift is None else shift - c
+            elif kind == "sub":
+                shift = c if shift is None else c - shift
+                mult = -1.0 if mult is None else -mult
+            else:
+                shift = None if shift is None else shift * c
+                mult = c if mult is None else mult * c
+        finally:
+            self._bypass = False
+
+        def replay(real, c=c, left=left, func=func, reflected=reflected):
+            operands = (real, c) if left else (c, real)
+            return func(*(operands[::-1] if reflected else operands))
+        derived = DeferredGather(table=info.table, index=info.index, shape=info.shape, shift=shift,
+                                 mult=mult, link="identity", parent=info, replay=replay,
+                                 chain=info.chain + ((kind, c, left),))
+        return self._gather_placeholder(ph, derived)
+
+    def _materialize_gather(self, info: DeferredGather) -> torch.Tensor:
+        if info.real is None:
+            if info.parent is None:
+                _guide.flush_draws()   # the table may be a guide draw not launched yet
+            else:
+                real = self._materialize_gather(info.parent)
+            self._bypass = True
+            try:
+                info.real = info.replay() if info.parent is None else info.replay(real)
+            finally:
+                self._bypass = False
+        return info.real
 
     def _eligible(self, args, kwargs, matrix: bool = False) -> bool:
         """``matrix``: the call is a matmul (not ``mv``), which also takes a [P, C] theta."""
@@ -168,6 +330,9 @@ class DeferredMatmul(TorchFunctionMode):
         """
         The real value of a placeholder (computed once), or ``tensor`` itself.
         """
+        gathered = self.lookup_gather(tensor)
+        if gathered is not None:
+            return self._materialize_gather(gathered)
         info = self.lookup(tensor)
         if info is None:
             return tensor
@@ -209,34 +374,44 @@ class DeferredMatmul(TorchFunctionMode):
             X, theta = args
             info = Deferred(X=X, theta=theta, shape=torch.Size((X.shape[0],) + tuple(theta.shape[1:])))
             return self._placeholder(theta, info.shape, info)
-        if not self.deferred and not _guide._LAZY and \
+        if self.defer_gather and (func in _GETITEMS or func in _INDEX_SELECTS):
+            call = self._gather_call(func, args, kwargs)
+            if call is not None:
+                table, index = call
+                info = DeferredGather(table=table, index=index, shape=torch.Size(index.shape),
+                                      replay=lambda: func(*args, **kwargs))
+                return self._gather_placeholder(table, info)
+        if not self.deferred and not self.gathers and not _guide._LAZY and \
                 (not _guide._PENDING_DRAWS or func in _METADATA or func in _BROADCASTS):
             # no placeholder exists, and no pending draw is read by this call: nothing to do
             return func(*args, **kwargs)
         touched = []
         lazy = []
+        gathered = []
         for x in _leaves(args, kwargs):
             info = self.lookup(x)
             if info is not None:
                 touched.append(info)
+            elif self.lookup_gather(x) is not None:
+                gathered.append(self.lookup_gather(x))
             elif lazy_of(x) is not None:
                 lazy.append(x)
             elif func not in _METADATA and func not in _BROADCASTS and \
                     _guide.pending_draw(x) is not None:
                 # the model reads a guide draw whose launch was left to the loss's planning
                 _guide.flush_draws()
-        if not touched and not lazy:
+        if not touched and not lazy and not gathered:
             return func(*args, **kwargs)
         if func in _METADATA:
             return func(*args, **kwargs)
         if func is torch.Tensor.type_as and len(args) == 2 and self.lookup(args[0]) is None and \
-                lazy_of(args[0]) is None:
+                self.lookup_gather(args[0]) is None and lazy_of(args[0]) is None:
             # `x.type_as(placeholder)` reads the placeholder's dtype and device only (Binomial and
             # NegativeBinomial cast their total_count to their logits' type this way)
             return func(*args, **kwargs)
         if lazy and func not in _BROADCASTS:
             raise NeedsDraws(getattr(func, "__name__", str(func)))
-        if not touched:
+        if not touched and not gathered:
             return func(*args, **kwargs)
         if func in _BROADCASTS:
             out = func(*args, **kwargs)
@@ -246,9 +421,26 @@ class DeferredMatmul(TorchFunctionMode):
                 outs = list(out)
                 for src, dst in zip(inputs, outs):
                     self._derive(src, dst)
+                    if gathered and isinstance(src, torch.Tensor) and src.dim() == 0 and \
+                            self.lookup(src) is None and self.lookup_gather(src) is None:
+                        self.sources[id(dst)] = src
+                        self._keep.append(dst)
             else:
                 self._derive(args[0], out)
             return out
+        if gathered and not touched:
+            if func in _EXPS and len(args) == 1 and not kwargs and gathered[0].link == "identity":
+                info = gathered[0]
+                derived = DeferredGather(table=info.table, index=info.index, shape=info.shape,
+                                         shift=info.shift, mult=info.mult, link="exp", parent=info,
+                                         replay=lambda real: func(real), chain=info.chain)
+                return self._gather_placeholder(args[0], derived)
+            out = self._affine(func, args, kwargs)
+            if out is not None:
+                return out
+        if not touched:
+            args, kwargs = tree_map(lambda x: self.materialize(x), (args, kwargs))
+            return func(*args, **kwargs)
         if func in _EXPS and len(args) == 1 and not kwargs and touched[0].link == "identity":
             info = touched[0]
             root = info.root or info
@@ -258,8 +450,7 @@ class DeferredMatmul(TorchFunctionMode):
         derived = self._softmax_link(func, args, kwargs)
         if derived is not None:
             return self._placeholder(args[0], derived.shape, derived)
-        args, kwargs = tree_map(lambda x: self.materialize(x) if self.lookup(x) else x,
-                                (args, kwargs))
+        args, kwargs = tree_map(lambda x: self.materialize(x), (args, kwargs))
         return func(*args, **kwargs)
 
     def _softmax_link(self, func: Callable, args, kwargs) -> Optional[Deferred]:
@@ -297,6 +488,15 @@ class DeferredMatmul(TorchFunctionMode):
         return None
 
     def _derive(self, src: Any, dst: torch.Tensor) -> None:
+        gathered = self.lookup_gather(src)
+        if gathered is not None and isinstance(dst, torch.Tensor):
+            shape = torch.Size(dst.shape)
+            self.gathers[id(dst)] = DeferredGather(
+                table=gathered.table, index=gathered.index, shape=shape, shift=gathered.shift,
+                mult=gathered.mult, link=gathered.link, parent=gathered,
+                replay=lambda real: real.expand(shape), chain=gathered.chain)
+            self._keep.append(dst)
+            return
         info = self.lookup(src)
         if info is None or not isinstance(dst, torch.Tensor):
             return

@@ -120,6 +120,28 @@ class SiteRecord:
                               # Categorical's logits over a [P, C] theta, "log_softmax"
     order: int = 0   # position of the sample statement in the model (errors raise in this order)
     extra: float = 0.0   # the family's constant fourth input (mi_site.extra): StudentT's df
+    # Group-indexed site (a parameter role = link(shift + mult * table[index]) deferred by
+    # mininf_amd.linear): per parameter role None or a GatherRole; after tracing its table is
+    # [K, G] and its tensor terms are [K].
+    gather_roles: Optional[List[Optional["GatherRole"]]] = None
+    gather: Any = None        # engine: the mi_gather_site launcher
+
+
+@dataclasses.dataclass
+class GatherRole:
+    """One gathered parameter role of a site: ``link(shift + mult * table[:, index])``."""
+    index: torch.Tensor               # the model's 1-D integer index [N] (unbatched)
+    link: str                         # "identity" or "exp"
+    table_output: int                 # output indices of the vmapped trace (-1: none)
+    shift_output: int = -1
+    mult_output: int = -1
+    shift: Any = None                 # None, a Python number or, after tracing, a [K] tensor
+    mult: Any = None
+    table: Optional[torch.Tensor] = None   # after tracing: [K, G]
+    # the model's own operations on the gather, in order: ("add" | "sub" | "mul", c, left) with c a
+    # Python number or (an output index, after tracing a [K] tensor) and the gather the left
+    # operand or not; shift and mult are their composition
+    chain: List[Tuple[str, Any, bool]] = dataclasses.field(default_factory=list)
 
 
 @dataclasses.dataclass
@@ -600,10 +622,19 @@ class ParticleTracer(TracerMixin):
                     all(mode.lookup(p) is None for j, p in enumerate(params) if j != role):
                 linear = info.root or info
                 link = info.link
-            params = [p if (linear is not None and j == role) else mode.materialize(p)
-                      for j, p in enumerate(params)]
+            gathered = self._gathered_roles(mode, family, distribution, params, data, shape) \
+                if linear is None else None
+            if gathered is not None:
+                # the other roles: the scalar a broadcast beside the placeholder came from
+                params = [p if g is not None else mode.sources.get(id(p), mode.materialize(p))
+                          for p, g in zip(params, gathered)]
+            else:
+                params = [p if (linear is not None and j == role) else mode.materialize(p)
+                          for j, p in enumerate(params)]
             if family in ("dirichlet", "mixture_normal"):
                 data = mode.materialize(data)
+        else:
+            gathered = None
 
         # Value support is checked by the site kernels (fused flag); constraint checks on the
         # parameters as well (MI_FLAG_PARAM), replacing torch's validate_args at construction.
@@ -615,8 +646,45 @@ class ParticleTracer(TracerMixin):
             record.linear_X = linear.X
             record.linear_theta_index = self._emit(linear.theta)
             record.linear_role, record.linear_link = role, link
+        if gathered is not None:
+            record.gather_roles = [None if g is None else GatherRole(
+                index=g.index, link=g.link, table_output=self._emit(g.table),
+                shift_output=self._emit(g.shift) if isinstance(g.shift, torch.Tensor) else -1,
+                mult_output=self._emit(g.mult) if isinstance(g.mult, torch.Tensor) else -1,
+                shift=g.shift, mult=g.mult,
+                chain=[(op, ("output", self._emit(c)) if isinstance(c, torch.Tensor) else c, left)
+                       for op, c, left in g.chain]) for g in gathered]
         self.sites.append(record)
         return value
+
+    @staticmethod
+    def _gathered_roles(mode, family: str, distribution: Distribution, params: List[Any],
+                        data: torch.Tensor, shape: torch.Size):
+        """
+        Per parameter role the gather placeholder (``linear.DeferredGather``) a gathered site
+        evaluates inside its kernel, or None for a site that is not one: a Normal,
+        Bernoulli-logits or Poisson (rate = exp of the predictor) site over an unbatched value of
+        shape (N,) whose gathered roles share one index [N] and carry a link the family takes,
+        with no deferred matmul among the other roles.
+        """
+        infos = [mode.lookup_gather(p) for p in params]
+        if not any(info is not None for info in infos):
+            return None
+        if family not in ("normal", "bernoulli_logits", "poisson") or \
+                (family == "bernoulli_logits" and "logits" not in distribution.__dict__):
+            return None
+        want = "exp" if family == "poisson" else "identity"
+        live = [info for info in infos if info is not None]
+        index = live[0].index
+        N = index.shape[0]
+        if any(info.link != want or info.index is not index or tuple(info.shape) != (N,)
+               for info in live):
+            return None
+        if is_batched(data) or tuple(data.shape) != (N,) or tuple(shape) != (N,):
+            return None
+        if any(mode.lookup(p) is not None for p in params):
+            return None
+        return infos
 
     def _check_parameters(self, name: str, distribution: Distribution) -> None:
         """
@@ -772,16 +840,17 @@ def _trace(model: Callable, samples: Dict[str, torch.Tensor], K: int, validate: 
 
     if defer_matmul is None:
         defer_matmul = switches.enabled("DEFER_MATMUL")
+    defer_gather = switches.enabled("DEFER_GATHER")
     names = list(samples)
     tracer = ParticleTracer(validate=validate)
 
     from .guide import _LAZY, flush_draws
-    use_mode = defer_matmul or bool(_LAZY)
+    use_mode = defer_matmul or defer_gather or bool(_LAZY)
     if not use_mode:
         flush_draws()   # no mode watches the model's reads of deferred guide draws
 
     def per_particle(*values):
-        mode = DeferredMatmul(K, defer_matmul) if use_mode else None
+        mode = DeferredMatmul(K, defer_matmul, defer_gather) if use_mode else None
         tracer.deferred = mode
         with tracer, contextlib.ExitStack() as stack:
             if lift is not None:
@@ -812,6 +881,15 @@ def _trace(model: Callable, samples: Dict[str, torch.Tensor], K: int, validate: 
         site.tensors = [outputs[index] for index in site.roles]
         if site.linear_theta_index >= 0:
             site.linear_theta = outputs[site.linear_theta_index]
+        for g in site.gather_roles or ():
+            if g is not None:
+                g.table = outputs[g.table_output]
+                if g.shift_output >= 0:
+                    g.shift = outputs[g.shift_output]
+                if g.mult_output >= 0:
+                    g.mult = outputs[g.mult_output]
+                g.chain = [(op, outputs[c[1]] if isinstance(c, tuple) else c, left)
+                           for op, c, left in g.chain]
     checks = [(check, outputs[check.output]) for check in tracer.checks]
     fallback = [(name, outputs[index]) for name, index in tracer.fallback_outputs]
     return ParticleTrace(sites=tracer.sites, checks=checks, fallback=fallback, K=K)

@@ -22,6 +22,7 @@ SWITCHES = {
     "MVN_KERNEL": (True, "native MultivariateNormal log density"),
     "CHOLESKY_KERNEL": (True, "native batched Cholesky factorisation"),
     "DEFER_MATMUL": (True, "leave a model's X @ theta to the linear site kernel"),
+    "DEFER_GATHER": (True, "leave a model's alpha[group] to the gathered site kernel"),
     "FUSE_ROWS": (True, "a linear launch draws its minibatch's rows itself"),
     "DRAW_IN_LINEAR": (True, "a linear launch draws the guide's theta itself"),
     "BETA_DGRAD": (False, "compute the Beta implicit-gradient factors on a side stream"),
