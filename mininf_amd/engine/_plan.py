@@ -14,6 +14,7 @@ import torch
 
 from .. import _native as nat
 from .. import data, guide, particles, switches
+from ..linear import put_back
 from ..particles import ParticleTrace, SiteRecord
 from ._groups import _QUERY_ADDRESS, _GroupLauncher
 from ._held import flush_pending_step, pending_step
@@ -199,11 +200,7 @@ def plan_linear(trace: ParticleTrace, g0: float, device: torch.device,
                     if cb is not None:
                         launcher.count_src = batch.loader.columns[cb[1]]
         if launcher is None:
-            # materialise the predictor as the model would have: [K, N] = theta @ X^T
-            guide.flush_draws(claimed=True)
-            real = theta @ site.linear_X.t()
-            site.tensors[site.linear_role] = real.exp() if site.linear_link == "exp" else real
-            site.linear_X = None
+            put_back(site, K)   # the predictor as the model would have: theta @ X^T
             continue
         launcher.draw = (claims or {}).get(id(site))
         out.append(launcher)

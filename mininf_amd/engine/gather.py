@@ -19,8 +19,9 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from .. import _native as nat
-from .. import data, guide
-from ..particles import GatherRole, SiteRecord
+from .. import data
+from ..linear import put_back as _materialise   # (the gather back as the model wrote it)
+from ..particles import SiteRecord
 from ._operands import FAMILY_CODES, _collapse, _to_device
 
 # Index plans by (data pointer, shape, stride, dtype, device, G): (weakref to the index, its
@@ -246,30 +247,6 @@ class _GatherSiteFn(torch.autograd.Function):
                                                   ctx.g0, nat.stream_handle(g.device)),
                           "mi_scale_rows")
         return (None, None, None, *ctx.grads, None, None)
-
-
-def _replay(g: GatherRole, K: int) -> torch.Tensor:
-    """The role as the model computed it: table[:, index], then the model's own operations in
-    their order (the same elementwise roundings as under vmap), then the link."""
-    real = g.table[:, g.index]
-    for op, c, left in g.chain:
-        c = c.reshape(K, 1) if isinstance(c, torch.Tensor) else c
-        if op == "add":
-            real = real + c if left else c + real
-        elif op == "sub":
-            real = real - c if left else c - real
-        else:
-            real = real * c if left else c * real
-    return real.exp() if g.link == "exp" else real
-
-
-def _materialise(site: SiteRecord, K: int) -> None:
-    """Put the model's own gather back, with the operations the model applied to it."""
-    guide.flush_draws(claimed=True)
-    for r, g in enumerate(site.gather_roles):
-        if g is not None:
-            site.tensors[r] = _replay(g, K)
-    site.gather_roles = None
 
 
 def plan_gather(site: SiteRecord, K: int, device: torch.device):

@@ -14,7 +14,8 @@ from typing import Optional
 import torch
 
 from .. import _native as nat
-from .. import data, guide
+from .. import data
+from ..linear import put_back
 from ..particles import SiteRecord
 from ._operands import _collapse, _to_device
 from ._rows import _run_categorical
@@ -155,7 +156,5 @@ def plan_softmax(site: SiteRecord, K: int, device: torch.device):
                 launcher.batch, launcher.X_src, launcher.value_src = None, X, value
         site.softmax = launcher
         return site, (theta,), value, mask
-    guide.flush_draws(claimed=True)
-    site.tensors[site.linear_role] = torch.matmul(X, theta)
-    site.linear_X = None
+    put_back(site, K)
     return None

@@ -1,45 +1,51 @@
 """
-Deferred linear predictors: ``X @ theta`` inside a traced model without the [N, K] product.
+Deferred predictors: ``X @ theta`` and ``alpha[group]`` inside a traced model without the [N, K]
+product or gather.
 
 The reference's regression models compute ``Normal(X @ theta, sigma)`` (``tests/test_mininf.py:13-18``,
 ``examples/minibatch.md:24-33``). Traced over K particles that matmul is a [N, K] GEMM whose output is
 only ever read by the site's log density. While :func:`mininf_amd.particles.trace_particles` runs the
-model, :class:`DeferredMatmul` (a ``TorchFunctionMode``) intercepts ``matmul(X, theta)`` for an
-observed 2-D ``X`` and a per-particle 1-D ``theta`` and returns a *placeholder*: a batched tensor of
-the right shape backed by a zero-stride zero, costing no memory and no kernel. The particle tracer
-turns a Normal / Bernoulli-logits site whose location / logits is such a placeholder into a fused
-linear site (``mi_linear_forward``: the product is evaluated inside the site kernel). So are the
-count regressions: a Binomial / NegativeBinomial whose ``logits`` is a placeholder, and a Poisson
-whose ``rate`` is ``exp`` of one -- ``torch.exp`` / ``Tensor.exp`` of a placeholder is a placeholder
-tagged with the *link* ``exp`` (the log link of the regression), which materialises to ``exp`` of
-the real product.
+model, :class:`DeferredMatmul` (a ``TorchFunctionMode``) answers such a call with a *placeholder*: a
+batched tensor of the right shape backed by a zero-stride scalar that is never read, costing no
+memory and no kernel, with one record (:class:`Deferred`) in the mode's table. The tracer turns a
+site whose parameter is still a placeholder into a fused site, whose kernel evaluates the predictor
+(``mi_linear_forward``, ``mi_softmax_linear_forward``, ``mi_gather_site_forward``).
 
-The multi-class regression ``Categorical(logits=X @ Theta)`` with a per-particle matrix ``Theta``
-[P, C] is deferred the same way (``torch.matmul`` only; the placeholder has shape [N, C]).
-``Categorical.__init__`` normalises its logits, ``logits - logits.logsumexp(dim=-1, keepdim=True)``:
-``logsumexp`` of such a placeholder over its last dimension (``keepdim=True``) is a placeholder
-[N, 1] with the link ``logsumexp``, the difference of the two (and ``log_softmax`` over the last
-dimension) one with the link ``log_softmax``; a ``log_softmax`` placeholder normalises again the
-same way (``Categorical(logits=torch.log_softmax(eta, -1))``). The tracer turns a Categorical site whose logits are
-an identity or ``log_softmax`` placeholder into a fused softmax site
-(``mi_softmax_linear_forward``).
+**Roots.** ``"matmul"``: ``matmul`` / ``mv`` of an observed float32 ``X`` [N, P] and a per-particle
+``theta`` [P] or (``matmul`` only) ``Theta`` [P, C], C <= ``MAX_CATEGORIES``: a placeholder [N] or
+[N, C]. ``"gather"``: ``table[index]`` (``__getitem__``, or ``index_select`` over dimension 0) of a
+per-particle float32 ``table`` [G] and an observed 1-D integer ``index`` [N]. The switches
+``MININF_AMD_DEFER_MATMUL=0`` / ``MININF_AMD_DEFER_GATHER=0`` turn them off.
 
-A parameter indexed by a group label, ``alpha[group]`` with a per-particle table ``alpha`` [G] and
-an observed 1-D integer ``group`` [N] (``Tensor.__getitem__`` or ``index_select`` over dimension
-0), is deferred the same way (:class:`DeferredGather`): the placeholder [N] stays one through
-broadcasting views, through ``add`` / ``sub`` / ``mul`` (and their reflected forms) with a Python
-number or a per-particle scalar -- they compose the affine predictor ``shift + mult * alpha[group]``
--- and through ``exp`` of it. The tracer turns a Normal / Bernoulli-logits / Poisson site whose
-parameter is such a placeholder into a gathered site (``mi_gather_site_forward``: the [K, N] gather
-and its scatter-add backward never run). ``MININF_AMD_DEFER_GATHER=0`` turns this off.
+**Derivations.** A call on a placeholder that a site kernel can still evaluate returns another
+placeholder, whose record holds its parent and the replay of the call on the parent's real value:
 
-Semantics are preserved for every other use: any torch operation that reads a placeholder's values
-(anything but shape queries and broadcasting views) first *materialises* it -- the real
-``torch.matmul(X, theta)`` is computed at that point, exactly as the model wrote it -- and the
-operation runs on the real tensor. A placeholder therefore never leaks a wrong value into the model.
+====================================  ======  =====================  ===========
+call                                  kind    link of ``ph``         new link
+====================================  ======  =====================  ===========
+broadcasting views                    either  any                    unchanged
+``exp(ph)``                           either  identity               exp
+``ph + c``, ``ph - c``, ``ph * c``    gather  identity               identity
+``ph.logsumexp(-1, keepdim=True)``    matmul  identity, log_softmax  logsumexp
+``log_softmax(ph, -1)``               matmul  identity, log_softmax  log_softmax
+``ph - lse``                          matmul  identity, log_softmax  log_softmax
+====================================  ======  =====================  ===========
+
+``exp`` is the log link of a Poisson rate. ``c`` is a Python number or a per-particle scalar, in the
+plain and the reflected forms: they compose ``shift + mult * table[index]``. The last three apply to
+a [.., N, C] placeholder of ``X @ Theta`` and are how ``Categorical.__init__`` normalises its logits
+(``logits - logits.logsumexp(dim=-1, keepdim=True)``: ``lse`` is the logsumexp placeholder of the
+same root after the same normalisations) and how a model does (``torch.log_softmax(eta, -1)``).
+Metadata queries and ``x.type_as(ph)`` read no values and pass a placeholder through.
+
+**Anything else materialises.** Every other torch operation that meets a placeholder first gets its
+real value -- the root's call as the model wrote it, computed once, then the replay of each
+derivation -- and runs on the real tensor, so a placeholder never leaks a wrong value into the
+model. After the trace, :func:`put_back` does the same for a site a planner's kernel cannot take.
 """
 from __future__ import annotations
 
+import contextlib
 import dataclasses
 from typing import Any, Callable, Dict, List, Optional, Tuple
 
@@ -67,31 +73,27 @@ _METADATA = {
     torch.Tensor.is_leaf.__get__, torch.Tensor.names.__get__,
 }
 
-# exp of an identity-link placeholder is a placeholder with the link "exp" (Poisson's log link).
-_EXPS = {torch.exp, torch.Tensor.exp}
-
-# The normalisation of Categorical's logits over a [N, C] placeholder (see the module docstring).
-_LOGSUMEXPS = {torch.logsumexp, torch.Tensor.logsumexp}
-_SUBS = {torch.sub, torch.Tensor.sub, torch.Tensor.__sub__}
-_LOG_SOFTMAXES = {torch.log_softmax, torch.Tensor.log_softmax, torch.nn.functional.log_softmax}
-
-# Most categories of a deferred `X @ Theta` (MI_SOFTMAX_LINEAR_MAX_C of include/mininf_amd.h).
-MAX_CATEGORIES = 32
-
 # Broadcasting views of a placeholder are placeholders of the broadcast shape (and the same link).
 _BROADCASTS = {torch.broadcast_tensors, torch.Tensor.expand, torch.Tensor.expand_as,
                torch.Tensor.broadcast_to, torch.broadcast_to}
 
-
-# A gather `table[index]` over dimension 0, and the arithmetic that keeps its placeholder one.
 _GETITEMS = {torch.Tensor.__getitem__}
 _INDEX_SELECTS = {torch.index_select, torch.Tensor.index_select}
+
+# The functions of the derivations. Arithmetic: True for a reflected form, func(x, y) = y op x.
+_EXPS = {torch.exp, torch.Tensor.exp}
+_LOGSUMEXPS = {torch.logsumexp, torch.Tensor.logsumexp}
+_LOG_SOFTMAXES = {torch.log_softmax, torch.Tensor.log_softmax, torch.nn.functional.log_softmax}
 _ADDS = {torch.add: False, torch.Tensor.add: False, torch.Tensor.__add__: False,
          torch.Tensor.__radd__: True}
 _MULS = {torch.mul: False, torch.Tensor.mul: False, torch.Tensor.__mul__: False,
          torch.Tensor.__rmul__: True}
-_SUBTRACTS = {torch.sub: False, torch.Tensor.sub: False, torch.Tensor.__sub__: False,
-              torch.Tensor.__rsub__: True}   # True: reflected, func(x, y) = y op x
+_SUBS = {torch.sub: False, torch.Tensor.sub: False, torch.Tensor.__sub__: False,
+         torch.Tensor.__rsub__: True}
+_ARITHMETIC = {"add": _ADDS, "sub": _SUBS, "mul": _MULS}
+
+# Most categories of a deferred `X @ Theta` (MI_SOFTMAX_LINEAR_MAX_C of include/mininf_amd.h).
+MAX_CATEGORIES = 32
 
 
 class NeedsDraws(Exception):
@@ -99,7 +101,6 @@ class NeedsDraws(Exception):
     Raised while tracing when the model uses a lazy guide draw (:class:`mininf_amd.guide.LazyDraw`)
     in an operation other than a site parameter / value: the loss then re-traces with real draws.
     """
-
 
 
 def _leaves(args, kwargs):
@@ -115,54 +116,85 @@ def _leaves(args, kwargs):
         elif isinstance(x, dict):
             stack.extend(x.values())
 
+
+def _last_dim(args, kwargs, ndim: int, extra: dict) -> bool:
+    """Whether a reduction ``func(ph, dim, **extra)`` runs over the last of ``ndim`` dimensions."""
+    rest = dict(kwargs)
+    rest.pop("_stacklevel", None)
+    dim = args[1] if len(args) > 1 else rest.pop("dim", None)
+    if len(args) > 2 or isinstance(dim, bool) or not isinstance(dim, int):
+        return False
+    return dim in (-1, ndim - 1) and rest == extra
+
+
 @dataclasses.dataclass
 class Deferred:
     """
-    ``root``: the deferred ``X @ theta`` (``X`` [N, P] observed, ``theta`` batched [P]); a derived
-    placeholder is ``root`` broadcast to ``shape``, then passed through ``link`` ("identity" or
-    "exp"). With ``theta`` batched [P, C] the root has shape [N, C], and the links "logsumexp"
-    (over the last dimension, kept) and "log_softmax" are applied before the broadcast.
-    """
-    X: torch.Tensor
-    theta: torch.Tensor
-    shape: torch.Size
-    root: Optional["Deferred"] = None
-    real: Optional[torch.Tensor] = None
-    link: str = "identity"
-    # the normalisations behind a "log_softmax" placeholder (or under a "logsumexp" one), in order:
-    # "sub" (x - x.logsumexp(-1, keepdim=True), as Categorical.__init__ writes it) or "log_softmax";
-    # Categorical(logits=torch.log_softmax(eta, -1)) normalises twice
-    steps: Tuple[str, ...] = ()
+    The record of one placeholder of ``shape`` (without the particle axis): ``replay`` applied to
+    the real value of ``parent`` gives its own, cached in ``real``; a root has no parent and its
+    ``replay()`` is the call the model wrote. ``link`` is what it stands for, as a function of the
+    root's predictor (see the module docstring).
 
+    ``"matmul"``: ``X`` and ``theta`` as the model passed them. ``steps`` lists the normalisations
+    behind a "log_softmax" placeholder (or under a "logsumexp" one), in order: "sub"
+    (``x - x.logsumexp(-1, keepdim=True)``) or "log_softmax". Every derived record hangs off its
+    root: its replay is the whole path from the product.
 
-@dataclasses.dataclass
-class DeferredGather:
+    ``"gather"``: ``link(shift + mult * table[index])`` with ``shift`` / ``mult`` None (0 / 1), a
+    Python number or a per-particle (batched 0-d) tensor. ``chain`` lists the affine operations, in
+    order, for :func:`put_back`: ("add" | "sub" | "mul", c, left), the placeholder the left
+    operand or not.
     """
-    A placeholder of ``link(shift + mult * table[index])`` broadcast to ``shape``: ``table`` batched
-    [G], ``index`` an observed 1-D integer tensor [N], ``shift`` / ``mult`` None (0 / 1), a Python
-    number or a per-particle (batched 0-d) tensor, ``link`` "identity" or "exp". ``parent`` and
-    ``replay`` materialise it: the parent's real value passed through the operation as the model
-    wrote it (the root: the gather itself). ``chain`` lists those operations, in order, for a
-    planner that has to put the gather back after the trace: ("add" | "sub" | "mul", c, left) with
-    the placeholder the left operand or not.
-    """
-    table: torch.Tensor
-    index: torch.Tensor
+    kind: str
     shape: torch.Size
-    shift: Any = None
-    mult: Any = None
     link: str = "identity"
-    parent: Optional["DeferredGather"] = None
+    parent: Optional["Deferred"] = None
     replay: Optional[Callable] = None
     real: Optional[torch.Tensor] = None
+    X: Optional[torch.Tensor] = None
+    theta: Optional[torch.Tensor] = None
+    steps: Tuple[str, ...] = ()
+    table: Optional[torch.Tensor] = None
+    index: Optional[torch.Tensor] = None
+    shift: Any = None
+    mult: Any = None
     chain: Tuple[Tuple[str, Any, bool], ...] = ()
+
+    @property
+    def root(self) -> "Deferred":
+        info = self
+        while info.parent is not None:
+            info = info.parent
+        return info
+
+    def derived(self, **changes) -> "Deferred":
+        """A record derived from this one: a copy with ``changes`` and no real value yet."""
+        new = object.__new__(Deferred)   # (dataclasses.replace costs microseconds on every trace)
+        new.__dict__.update(self.__dict__)
+        new.__dict__.update(changes, parent=self, real=None)
+        return new
+
+
+def _matmul_derived(root: Deferred, shape, link: str, steps: Tuple[str, ...] = ()) -> Deferred:
+    """The record of ``link`` of the product ``root`` after ``steps``, broadcast to ``shape``."""
+    shape = torch.Size(shape)
+
+    def replay(real):
+        for step in steps:   # each as the model wrote it
+            real = torch.log_softmax(real, -1) if step == "log_softmax" else \
+                real - real.logsumexp(dim=-1, keepdim=True)
+        if link == "logsumexp":
+            real = real.logsumexp(dim=-1, keepdim=True)
+        real = real.expand(shape)
+        return real.exp() if link == "exp" else real
+    return root.derived(shape=shape, link=link, steps=steps, replay=replay)
 
 
 class DeferredMatmul(TorchFunctionMode):
     """
     Active while a model is traced over particles (inside ``vmap``); see the module docstring.
     """
-    require_device = True   # defer only device matmuls (the fused kernel's operands)
+    require_device = True   # defer only device operands (the fused kernels')
 
     def __init__(self, K: int, defer_matmul: bool = True,
                  defer_gather: Optional[bool] = None) -> None:
@@ -171,8 +203,7 @@ class DeferredMatmul(TorchFunctionMode):
         self.defer_matmul = defer_matmul
         self.defer_gather = switches.enabled("DEFER_GATHER") if defer_gather is None \
             else defer_gather
-        self.deferred: Dict[int, Deferred] = {}
-        self.gathers: Dict[int, DeferredGather] = {}
+        self.deferred: Dict[int, Deferred] = {}   # id(placeholder) -> its record
         # per-particle scalars broadcast beside a gather placeholder (Normal's broadcast_all of
         # loc and scale): the broadcast view -> the scalar it came from
         self.sources: Dict[int, torch.Tensor] = {}
@@ -180,15 +211,97 @@ class DeferredMatmul(TorchFunctionMode):
         self._bypass = False
 
     # ---- helpers ---------------------------------------------------------------------------
-    def lookup(self, tensor: Any) -> Optional[Deferred]:
-        if isinstance(tensor, torch.Tensor):
-            return self.deferred.get(id(tensor))
-        return None
+    @contextlib.contextmanager
+    def _bypassed(self):
+        """Torch calls made inside run as they are (the mode's own calls on real tensors)."""
+        self._bypass = True
+        try:
+            yield
+        finally:
+            self._bypass = False
 
-    def lookup_gather(self, tensor: Any) -> Optional[DeferredGather]:
-        if isinstance(tensor, torch.Tensor):
-            return self.gathers.get(id(tensor))
-        return None
+    def lookup(self, tensor: Any, kind: Optional[str] = None) -> Optional[Deferred]:
+        """The record of a placeholder (of ``kind``, if given), or None."""
+        info = self.deferred.get(id(tensor)) if isinstance(tensor, torch.Tensor) else None
+        return info if info is None or kind is None or info.kind == kind else None
+
+    def _accepted(self, tensor: Any, kind: Optional[str], links: Tuple[str, ...]) -> Optional[Deferred]:
+        """The record of a placeholder of ``kind`` whose link is one of ``links``, or None."""
+        info = self.lookup(tensor, kind)
+        return info if info is not None and info.link in links else None
+
+    def _placeholder(self, like: torch.Tensor, info: Deferred) -> torch.Tensor:
+        level = _functorch.maybe_get_level(like)
+        # never read (any value-reading use materialises the record): no initialising kernel
+        device = (info.X if info.kind == "matmul" else info.table).device
+        base = torch.empty((), dtype=torch.float32, device=device)
+        base = base.expand((self.K,) + tuple(info.shape))
+        out = _functorch._add_batch_dim(base, 0, level)
+        self.deferred[id(out)] = info
+        self._keep.append(out)
+        return out
+
+    def _derive(self, src: Any, dst: Any) -> None:
+        """``dst`` is a broadcasting view of ``src``: a placeholder if ``src`` is one."""
+        info = self.lookup(src)
+        if info is None or not isinstance(dst, torch.Tensor):
+            return
+        shape = torch.Size(dst.shape)
+        if info.kind == "matmul":
+            derived = _matmul_derived(info.root, shape, info.link, info.steps)
+        else:
+            derived = info.derived(shape=shape, replay=lambda real: real.expand(shape))
+        self.deferred[id(dst)] = derived
+        self._keep.append(dst)
+
+    def _real(self, info: Deferred) -> torch.Tensor:
+        if info.real is None:
+            if info.parent is None:
+                _guide.flush_draws()   # theta / the table may be a guide draw not launched yet
+                with self._bypassed():
+                    info.real = info.replay()
+            else:
+                real = self._real(info.parent)
+                with self._bypassed():
+                    info.real = info.replay(real)
+        return info.real
+
+    def materialize(self, tensor: torch.Tensor) -> torch.Tensor:
+        """
+        The real value of a placeholder (computed once), or ``tensor`` itself.
+        """
+        info = self.lookup(tensor)
+        return tensor if info is None else self._real(info)
+
+    def _scalar(self, x: Any) -> bool:
+        """A Python number or a per-particle float32 scalar: a term of the affine predictor."""
+        if isinstance(x, bool):
+            return False
+        if isinstance(x, (int, float)):
+            return True
+        return isinstance(x, torch.Tensor) and _functorch.is_batchedtensor(x) and x.dim() == 0 and \
+            x.dtype == torch.float32 and self.lookup(x) is None and lazy_of(x) is None
+
+    # ---- the creation rules ------------------------------------------------------------------
+    def _eligible(self, args, kwargs, matrix: bool = False) -> bool:
+        """``matrix``: the call is a matmul (not ``mv``), which also takes a [P, C] theta."""
+        if kwargs or len(args) != 2:
+            return False
+        X, theta = args
+        if not (isinstance(X, torch.Tensor) and isinstance(theta, torch.Tensor)):
+            return False
+        if self.lookup(X) is not None or self.lookup(theta) is not None:
+            return False   # (the product of a placeholder reads its values)
+        if not self.defer_matmul or lazy_of(X) is not None or lazy_of(theta) is not None:
+            return False
+        return (not _functorch.is_batchedtensor(X) and X.dim() == 2 and
+                (X.is_cuda or not self.require_device) and
+                X.dtype == torch.float32 and not X.requires_grad and
+                _functorch.is_batchedtensor(theta) and
+                (theta.dim() == 1 or (matrix and theta.dim() == 2 and
+                                      2 <= theta.shape[1] <= MAX_CATEGORIES)) and
+                theta.dtype == torch.float32 and theta.shape[0] == X.shape[1] and
+                X.shape[1] <= 64 and X.shape[0] > 0)
 
     def _gather_call(self, func: Callable, args, kwargs):
         """(table, index) of a call that is ``table[index]`` over a per-particle 1-D float32
@@ -209,8 +322,8 @@ class DeferredMatmul(TorchFunctionMode):
             return None
         if not (isinstance(table, torch.Tensor) and isinstance(index, torch.Tensor)):
             return None
-        if self.lookup(table) is not None or self.lookup_gather(table) is not None or \
-                lazy_of(table) is not None or lazy_of(index) is not None:
+        if self.lookup(table) is not None or lazy_of(table) is not None or \
+                lazy_of(index) is not None:
             return None
         if not (_functorch.is_batchedtensor(table) and table.dim() == 1 and
                 table.dtype == torch.float32 and table.shape[0] > 0 and
@@ -222,148 +335,89 @@ class DeferredMatmul(TorchFunctionMode):
             return None
         return table, index
 
-    def _gather_placeholder(self, like: torch.Tensor, info: DeferredGather) -> torch.Tensor:
-        level = _functorch.maybe_get_level(like)
-        base = torch.empty((), dtype=torch.float32, device=info.table.device)
-        base = base.expand((self.K,) + tuple(info.shape))
-        out = _functorch._add_batch_dim(base, 0, level)
-        self.gathers[id(out)] = info
-        self._keep.append(out)
-        return out
-
-    def _scalar(self, x: Any) -> bool:
-        """A Python number or a per-particle float32 scalar: a term of the affine predictor."""
-        if isinstance(x, bool):
-            return False
-        if isinstance(x, (int, float)):
-            return True
-        return isinstance(x, torch.Tensor) and _functorch.is_batchedtensor(x) and x.dim() == 0 and \
-            x.dtype == torch.float32 and self.lookup(x) is None and \
-            self.lookup_gather(x) is None and lazy_of(x) is None
-
-    def _affine(self, func: Callable, args, kwargs) -> Optional[torch.Tensor]:
-        """The placeholder of ``ph + c``, ``ph - c``, ``c - ph`` or ``ph * c`` for an identity-link
-        gather placeholder ``ph`` and a scalar ``c``; None for anything else."""
-        kind = "add" if func in _ADDS else "mul" if func in _MULS else \
-            "sub" if func in _SUBTRACTS else None
-        if kind is None or kwargs or len(args) != 2:
+    # ---- the derivations: each returns the derived record of a call it accepts, or None --------
+    def _exp(self, func: Callable, args, kwargs) -> Optional[Deferred]:
+        """``exp(ph)`` of an identity-link placeholder of either kind: the link "exp"."""
+        if func not in _EXPS or len(args) != 1 or kwargs:
             return None
-        reflected = (_ADDS if kind == "add" else _MULS if kind == "mul" else _SUBTRACTS)[func]
+        info = self._accepted(args[0], None, ("identity",))
+        if info is None:
+            return None
+        if info.kind == "matmul":
+            return _matmul_derived(info.root, info.shape, "exp")
+        return info.derived(link="exp", replay=func)
+
+    def _affine(self, func: Callable, args, kwargs) -> Optional[Deferred]:
+        """``ph + c``, ``ph - c``, ``c - ph`` or ``ph * c`` for an identity-link gather placeholder
+        ``ph`` and a scalar ``c``: the same link, with the term composed into shift / mult."""
+        op = next((op for op, funcs in _ARITHMETIC.items() if func in funcs), None)
+        if op is None or kwargs or len(args) != 2:
+            return None
+        reflected = _ARITHMETIC[op][func]
         x, y = (args[1], args[0]) if reflected else args   # the call computes x op y
-        if self.lookup_gather(x) is not None and self._scalar(y):
+        if self.lookup(x, "gather") is not None and self._scalar(y):
             ph, c, left = x, y, True
-        elif self.lookup_gather(y) is not None and self._scalar(x):
+        elif self.lookup(y, "gather") is not None and self._scalar(x):
             ph, c, left = y, x, False
         else:
             return None
-        info = self.lookup_gather(ph)
-        if info.link != "identity":
+        info = self._accepted(ph, "gather", ("identity",))
+        if info is None:
             return None
         shift, mult = info.shift, info.mult
-        self._bypass = True   # (per-particle scalars: [K] operations)
-        try:
-            if kind == "add":
+        with self._bypassed():   # (per-particle scalars: [K] operations)
+            if op == "add":
                 shift = c if shift is None else shift + c
-            elif kind == "sub" and left:
+            elif op == "sub" and left:
                 shift = -c if shift is None else shift - c
-            elif kind == "sub":
+            elif op == "sub":
                 shift = c if shift is None else c - shift
                 mult = -1.0 if mult is None else -mult
             else:
                 shift = None if shift is None else shift * c
                 mult = c if mult is None else mult * c
-        finally:
-            self._bypass = False
 
-        def replay(real, c=c, left=left, func=func, reflected=reflected):
+        def replay(real):
             operands = (real, c) if left else (c, real)
             return func(*(operands[::-1] if reflected else operands))
-        derived = DeferredGather(table=info.table, index=info.index, shape=info.shape, shift=shift,
-                                 mult=mult, link="identity", parent=info, replay=replay,
-                                 chain=info.chain + ((kind, c, left),))
-        return self._gather_placeholder(ph, derived)
+        return info.derived(shift=shift, mult=mult, replay=replay,
+                            chain=info.chain + ((op, c, left),))
 
-    def _materialize_gather(self, info: DeferredGather) -> torch.Tensor:
-        if info.real is None:
-            if info.parent is None:
-                _guide.flush_draws()   # the table may be a guide draw not launched yet
-            else:
-                real = self._materialize_gather(info.parent)
-            self._bypass = True
-            try:
-                info.real = info.replay() if info.parent is None else info.replay(real)
-            finally:
-                self._bypass = False
-        return info.real
+    def _softmax_operand(self, args) -> Optional[Deferred]:
+        """The record of ``args[0]`` if a softmax normalisation may derive from it: a [.., N, C]
+        placeholder of ``X @ Theta``, raw or normalised already."""
+        info = self._accepted(args[0], "matmul", ("identity", "log_softmax")) if args else None
+        return info if info is not None and info.theta.dim() == 2 else None
 
-    def _eligible(self, args, kwargs, matrix: bool = False) -> bool:
-        """``matrix``: the call is a matmul (not ``mv``), which also takes a [P, C] theta."""
-        if kwargs or len(args) != 2:
-            return False
-        X, theta = args
-        if not (isinstance(X, torch.Tensor) and isinstance(theta, torch.Tensor)):
-            return False
-        if self.lookup(X) is not None or self.lookup(theta) is not None:
-            return False
-        if not self.defer_matmul or lazy_of(X) is not None or lazy_of(theta) is not None:
-            return False
-        return (not _functorch.is_batchedtensor(X) and X.dim() == 2 and
-                (X.is_cuda or not self.require_device) and
-                X.dtype == torch.float32 and not X.requires_grad and
-                _functorch.is_batchedtensor(theta) and
-                (theta.dim() == 1 or (matrix and theta.dim() == 2 and
-                                      2 <= theta.shape[1] <= MAX_CATEGORIES)) and
-                theta.dtype == torch.float32 and theta.shape[0] == X.shape[1] and
-                X.shape[1] <= 64 and X.shape[0] > 0)
+    def _logsumexp(self, func: Callable, args, kwargs) -> Optional[Deferred]:
+        """``logsumexp(ph, -1, keepdim=True)``: the link "logsumexp", [.., N, 1]."""
+        info = self._softmax_operand(args) if func in _LOGSUMEXPS else None
+        if info is None or not _last_dim(args, kwargs, len(info.shape), {"keepdim": True}):
+            return None
+        return _matmul_derived(info.root, tuple(info.shape[:-1]) + (1,), "logsumexp", info.steps)
 
-    def _placeholder(self, like: torch.Tensor, shape: torch.Size, info: Deferred) -> torch.Tensor:
-        level = _functorch.maybe_get_level(like)
-        # never read (any value-reading use materialises the product): no initialising kernel
-        base = torch.empty((), dtype=torch.float32, device=info.X.device)
-        base = base.expand((self.K,) + tuple(shape))
-        out = _functorch._add_batch_dim(base, 0, level)
-        self.deferred[id(out)] = info
-        self._keep.append(out)
-        return out
+    def _log_softmax(self, func: Callable, args, kwargs) -> Optional[Deferred]:
+        """``log_softmax(ph, -1)``: the link "log_softmax"."""
+        info = self._softmax_operand(args) if func in _LOG_SOFTMAXES else None
+        if info is None or not (_last_dim(args, kwargs, len(info.shape), {}) or
+                                _last_dim(args, kwargs, len(info.shape), {"dtype": None})):
+            return None
+        return _matmul_derived(info.root, info.shape, "log_softmax", info.steps + ("log_softmax",))
 
-    def materialize(self, tensor: torch.Tensor) -> torch.Tensor:
-        """
-        The real value of a placeholder (computed once), or ``tensor`` itself.
-        """
-        gathered = self.lookup_gather(tensor)
-        if gathered is not None:
-            return self._materialize_gather(gathered)
-        info = self.lookup(tensor)
-        if info is None:
-            return tensor
-        root = info.root or info
-        if root.real is None:
-            _guide.flush_draws()   # theta may be a guide draw not launched yet
-            self._bypass = True
-            try:
-                root.real = torch.matmul(root.X, root.theta)
-            finally:
-                self._bypass = False
-        if info.root is None:
-            return root.real
-        if info.real is None:
-            self._bypass = True
-            try:
-                if info.link in ("logsumexp", "log_softmax"):
-                    real = root.real
-                    for step in info.steps:   # each as the model wrote it
-                        real = torch.log_softmax(real, -1) if step == "log_softmax" else \
-                            real - real.logsumexp(dim=-1, keepdim=True)
-                    if info.link == "logsumexp":
-                        real = real.logsumexp(dim=-1, keepdim=True)
-                    info.real = real.expand(info.shape)
-                else:
-                    info.real = root.real.expand(info.shape)
-                    if info.link == "exp":
-                        info.real = info.real.exp()
-            finally:
-                self._bypass = False
-        return info.real
+    def _sub_logsumexp(self, func: Callable, args, kwargs) -> Optional[Deferred]:
+        """``ph - lse`` for the "logsumexp" placeholder ``lse`` of the same root after the same
+        normalisations: the link "log_softmax"."""
+        if _SUBS.get(func) is not False or len(args) != 2 or kwargs:
+            return None
+        info = self._softmax_operand(args)
+        other = self._accepted(args[1], "matmul", ("logsumexp",))
+        if info is None or other is None or other.root is not info.root or \
+                other.steps != info.steps or tuple(other.shape) != tuple(info.shape[:-1]) + (1,):
+            return None
+        return _matmul_derived(info.root, info.shape, "log_softmax", info.steps + ("sub",))
+
+    # tried in this order; a call none of them accepts materialises its placeholders
+    _DERIVATIONS = (_exp, _affine, _logsumexp, _log_softmax, _sub_logsumexp)
 
     # ---- the mode ----------------------------------------------------------------------------
     def __torch_function__(self, func: Callable, types, args=(), kwargs=None):
@@ -372,136 +426,98 @@ class DeferredMatmul(TorchFunctionMode):
             return func(*args, **kwargs)
         if func in _MATMULS and self._eligible(args, kwargs, func not in _MVS):
             X, theta = args
-            info = Deferred(X=X, theta=theta, shape=torch.Size((X.shape[0],) + tuple(theta.shape[1:])))
-            return self._placeholder(theta, info.shape, info)
+            info = Deferred("matmul", torch.Size((X.shape[0],) + tuple(theta.shape[1:])),
+                            X=X, theta=theta, replay=lambda: torch.matmul(X, theta))
+            return self._placeholder(theta, info)
         if self.defer_gather and (func in _GETITEMS or func in _INDEX_SELECTS):
             call = self._gather_call(func, args, kwargs)
             if call is not None:
                 table, index = call
-                info = DeferredGather(table=table, index=index, shape=torch.Size(index.shape),
-                                      replay=lambda: func(*args, **kwargs))
-                return self._gather_placeholder(table, info)
-        if not self.deferred and not self.gathers and not _guide._LAZY and \
+                info = Deferred("gather", torch.Size(index.shape), table=table, index=index,
+                                replay=lambda: func(*args, **kwargs))
+                return self._placeholder(table, info)
+        if not self.deferred and not _guide._LAZY and \
                 (not _guide._PENDING_DRAWS or func in _METADATA or func in _BROADCASTS):
             # no placeholder exists, and no pending draw is read by this call: nothing to do
             return func(*args, **kwargs)
-        touched = []
-        lazy = []
-        gathered = []
+        placeholders = []   # (the tensor, its record)
+        lazy = False
         for x in _leaves(args, kwargs):
-            info = self.lookup(x)
+            info = self.deferred.get(id(x))
             if info is not None:
-                touched.append(info)
-            elif self.lookup_gather(x) is not None:
-                gathered.append(self.lookup_gather(x))
+                placeholders.append((x, info))
             elif lazy_of(x) is not None:
-                lazy.append(x)
+                lazy = True
             elif func not in _METADATA and func not in _BROADCASTS and \
                     _guide.pending_draw(x) is not None:
                 # the model reads a guide draw whose launch was left to the loss's planning
                 _guide.flush_draws()
-        if not touched and not lazy and not gathered:
+        if not placeholders and not lazy:
             return func(*args, **kwargs)
         if func in _METADATA:
             return func(*args, **kwargs)
         if func is torch.Tensor.type_as and len(args) == 2 and self.lookup(args[0]) is None and \
-                self.lookup_gather(args[0]) is None and lazy_of(args[0]) is None:
+                lazy_of(args[0]) is None:
             # `x.type_as(placeholder)` reads the placeholder's dtype and device only (Binomial and
             # NegativeBinomial cast their total_count to their logits' type this way)
             return func(*args, **kwargs)
         if lazy and func not in _BROADCASTS:
             raise NeedsDraws(getattr(func, "__name__", str(func)))
-        if not touched and not gathered:
+        if not placeholders:
             return func(*args, **kwargs)
         if func in _BROADCASTS:
             out = func(*args, **kwargs)
-            inputs = args[0] if func is torch.broadcast_tensors and len(args) == 1 and \
-                isinstance(args[0], (list, tuple)) else args
             if func is torch.broadcast_tensors:
-                outs = list(out)
-                for src, dst in zip(inputs, outs):
+                inputs = args[0] if len(args) == 1 and isinstance(args[0], (list, tuple)) else args
+                gathered = any(info.kind == "gather" for _, info in placeholders)
+                for src, dst in zip(inputs, list(out)):
                     self._derive(src, dst)
                     if gathered and isinstance(src, torch.Tensor) and src.dim() == 0 and \
-                            self.lookup(src) is None and self.lookup_gather(src) is None:
+                            self.lookup(src) is None:
                         self.sources[id(dst)] = src
                         self._keep.append(dst)
             else:
                 self._derive(args[0], out)
             return out
-        if gathered and not touched:
-            if func in _EXPS and len(args) == 1 and not kwargs and gathered[0].link == "identity":
-                info = gathered[0]
-                derived = DeferredGather(table=info.table, index=info.index, shape=info.shape,
-                                         shift=info.shift, mult=info.mult, link="exp", parent=info,
-                                         replay=lambda real: func(real), chain=info.chain)
-                return self._gather_placeholder(args[0], derived)
-            out = self._affine(func, args, kwargs)
-            if out is not None:
-                return out
-        if not touched:
-            args, kwargs = tree_map(lambda x: self.materialize(x), (args, kwargs))
-            return func(*args, **kwargs)
-        if func in _EXPS and len(args) == 1 and not kwargs and touched[0].link == "identity":
-            info = touched[0]
-            root = info.root or info
-            derived = Deferred(X=root.X, theta=root.theta, shape=torch.Size(args[0].shape),
-                               root=root, link="exp")
-            return self._placeholder(args[0], derived.shape, derived)
-        derived = self._softmax_link(func, args, kwargs)
-        if derived is not None:
-            return self._placeholder(args[0], derived.shape, derived)
-        args, kwargs = tree_map(lambda x: self.materialize(x), (args, kwargs))
+        for derivation in self._DERIVATIONS:
+            derived = derivation(self, func, args, kwargs)
+            if derived is not None:
+                return self._placeholder(placeholders[0][0], derived)
+        args, kwargs = tree_map(self.materialize, (args, kwargs))
         return func(*args, **kwargs)
 
-    def _softmax_link(self, func: Callable, args, kwargs) -> Optional[Deferred]:
-        """
-        The derived placeholder of ``logsumexp(ph, -1, keepdim=True)``, ``ph - lse`` or
-        ``log_softmax(ph, -1)`` over a [.., N, C] identity placeholder ``ph``; None for anything else.
-        """
-        info = self.lookup(args[0]) if args else None
-        if info is None or info.link not in ("identity", "log_softmax") or \
-                (info.root or info).theta.dim() != 2:
-            return None
-        root = info.root or info
-        shape = tuple(args[0].shape)
 
-        def last_dim(extra) -> bool:
-            rest = dict(kwargs)
-            rest.pop("_stacklevel", None)
-            dim = args[1] if len(args) > 1 else rest.pop("dim", None)
-            if len(args) > 2 or isinstance(dim, bool) or not isinstance(dim, int):
-                return False
-            return dim in (-1, len(shape) - 1) and rest == extra
-
-        if func in _LOGSUMEXPS and last_dim({"keepdim": True}):
-            return Deferred(X=root.X, theta=root.theta, shape=torch.Size(shape[:-1] + (1,)),
-                            root=root, link="logsumexp", steps=info.steps)
-        if func in _LOG_SOFTMAXES and (last_dim({}) or last_dim({"dtype": None})):
-            return Deferred(X=root.X, theta=root.theta, shape=torch.Size(shape), root=root,
-                            link="log_softmax", steps=info.steps + ("log_softmax",))
-        if func in _SUBS and len(args) == 2 and not kwargs:
-            other = self.lookup(args[1])
-            if other is not None and other.link == "logsumexp" and other.root is root and \
-                    other.steps == info.steps and tuple(args[1].shape) == shape[:-1] + (1,):
-                return Deferred(X=root.X, theta=root.theta, shape=torch.Size(shape), root=root,
-                                link="log_softmax", steps=info.steps + ("sub",))
-        return None
-
-    def _derive(self, src: Any, dst: torch.Tensor) -> None:
-        gathered = self.lookup_gather(src)
-        if gathered is not None and isinstance(dst, torch.Tensor):
-            shape = torch.Size(dst.shape)
-            self.gathers[id(dst)] = DeferredGather(
-                table=gathered.table, index=gathered.index, shape=shape, shift=gathered.shift,
-                mult=gathered.mult, link=gathered.link, parent=gathered,
-                replay=lambda real: real.expand(shape), chain=gathered.chain)
-            self._keep.append(dst)
-            return
-        info = self.lookup(src)
-        if info is None or not isinstance(dst, torch.Tensor):
-            return
-        root = info.root or info
-        self.deferred[id(dst)] = Deferred(X=root.X, theta=root.theta,
-                                          shape=torch.Size(dst.shape), root=root, link=info.link,
-                                          steps=info.steps)
-        self._keep.append(dst)
+def put_back(site, K: int) -> None:
+    """
+    Restore what the model wrote where a planner's kernel cannot take a site recorded on a deferred
+    predictor (a :class:`mininf_amd.particles.SiteRecord` after the trace, with [K, ...] tensors):
+    the predictor becomes the site's own tensor and the record an ordinary site's.
+    """
+    _guide.flush_draws(claimed=True)
+    if site.gather_roles is not None:
+        # table[:, index], then the model's own operations in their order (the same elementwise
+        # roundings as under vmap), then the link
+        for r, g in enumerate(site.gather_roles):
+            if g is None:
+                continue
+            real = g.table[:, g.index]
+            for op, c, left in g.chain:
+                c = c.reshape(K, 1) if isinstance(c, torch.Tensor) else c
+                if op == "add":
+                    real = real + c if left else c + real
+                elif op == "sub":
+                    real = real - c if left else c - real
+                else:
+                    real = real * c if left else c * real
+            site.tensors[r] = real.exp() if g.link == "exp" else real
+        site.gather_roles = None
+        return
+    if site.family == "categorical":
+        # [K, N, C] logits; the row site normalises them, as Categorical does
+        real = torch.matmul(site.linear_X, site.linear_theta)
+    else:
+        real = site.linear_theta @ site.linear_X.t()   # [K, N]
+        if site.linear_link == "exp":
+            real = real.exp()
+    site.tensors[site.linear_role] = real
+    site.linear_X = None

@@ -591,50 +591,10 @@ class ParticleTracer(TracerMixin):
             self._record_torch_site(name, distribution, value, data, mask, scale)
             return value
 
-        # A deferred `X @ theta` as the location / logits of a Normal / Bernoulli-logits site over
-        # shared data becomes a fused linear site, and so do the count regressions: a Poisson whose
-        # rate is exp of it (the "exp" link), a Binomial / NegativeBinomial built with `logits=` it
-        # and a total_count that is data. Every other deferred parameter is materialised.
-        linear = None
-        role, link = 0, ""
-        mode = self.deferred
-        if mode is not None:
-            if family in ("binomial", "negative_binomial"):
-                role = 1
-                eligible = "logits" in distribution.__dict__ and not is_batched(params[0])
-            else:
-                eligible = family in ("normal", "bernoulli_logits", "poisson")
-            info = mode.lookup(params[role]) if params else None
-            if family == "categorical":
-                # Categorical(logits=X @ Theta), Theta [P, C] per particle: the softmax site
-                # normalises either way, so the raw product and its log_softmax are both taken
-                if info is not None and "logits" in distribution.__dict__ and \
-                        info.link in ("identity", "log_softmax") and \
-                        (info.root or info).theta.dim() == 2 and not is_batched(data) and \
-                        tuple(shape) == (info.X.shape[0],) and tuple(data.shape) == tuple(shape) and \
-                        tuple(info.shape) == tuple(shape) + (info.theta.shape[1],):
-                    linear = info.root or info
-                    link = info.link
-            elif info is not None and eligible and info.theta.dim() == 1 and \
-                    info.link == ("exp" if family == "poisson" else "identity") and \
-                    not is_batched(data) and tuple(shape) == (info.X.shape[0],) and \
-                    tuple(data.shape) == tuple(shape) and \
-                    all(mode.lookup(p) is None for j, p in enumerate(params) if j != role):
-                linear = info.root or info
-                link = info.link
-            gathered = self._gathered_roles(mode, family, distribution, params, data, shape) \
-                if linear is None else None
-            if gathered is not None:
-                # the other roles: the scalar a broadcast beside the placeholder came from
-                params = [p if g is not None else mode.sources.get(id(p), mode.materialize(p))
-                          for p, g in zip(params, gathered)]
-            else:
-                params = [p if (linear is not None and j == role) else mode.materialize(p)
-                          for j, p in enumerate(params)]
-            if family in ("dirichlet", "mixture_normal"):
-                data = mode.materialize(data)
-        else:
-            gathered = None
+        linear = gathered = None
+        if self.deferred is not None:
+            linear, gathered, params, data = self._deferred_predictor(
+                self.deferred, family, distribution, params, data, shape)
 
         # Value support is checked by the site kernels (fused flag); constraint checks on the
         # parameters as well (MI_FLAG_PARAM), replacing torch's validate_args at construction.
@@ -643,9 +603,9 @@ class ParticleTracer(TracerMixin):
                             mask=mask, description=type(distribution).__name__, order=self.order,
                             extra=extra)
         if linear is not None:
-            record.linear_X = linear.X
-            record.linear_theta_index = self._emit(linear.theta)
-            record.linear_role, record.linear_link = role, link
+            root, record.linear_role, record.linear_link = linear
+            record.linear_X = root.X
+            record.linear_theta_index = self._emit(root.theta)
         if gathered is not None:
             record.gather_roles = [None if g is None else GatherRole(
                 index=g.index, link=g.link, table_output=self._emit(g.table),
@@ -657,17 +617,63 @@ class ParticleTracer(TracerMixin):
         self.sites.append(record)
         return value
 
+    @classmethod
+    def _deferred_predictor(cls, mode, family: str, distribution: Distribution, params: List[Any],
+                            data: torch.Tensor, shape: torch.Size):
+        """
+        What a site records of the deferred predictors (``linear.Deferred``) among its parameters:
+        (linear, gathered, the parameters to emit, the value to emit). ``linear`` is (the root
+        ``X @ theta``, its role, its link) where the product is the location / logits of a Normal /
+        Bernoulli-logits site over shared data, the rate of a Poisson through ``exp``, the
+        ``logits=`` of a Binomial / NegativeBinomial whose total_count is data or those of a
+        Categorical; ``gathered`` is :meth:`_gathered_roles` of a site that is not linear. Every
+        other deferred parameter is materialised.
+        """
+        linear = None
+        role = 1 if family in ("binomial", "negative_binomial") else 0
+        info = mode.lookup(params[role], "matmul") if params else None
+        over_rows = info is not None and not is_batched(data) and \
+            tuple(shape) == (info.X.shape[0],) and tuple(data.shape) == tuple(shape)
+        if family == "categorical":
+            # Theta [P, C] per particle: the softmax site normalises either way, so the raw
+            # product and its log_softmax are both taken
+            if over_rows and "logits" in distribution.__dict__ and \
+                    info.link in ("identity", "log_softmax") and info.theta.dim() == 2 and \
+                    tuple(info.shape) == tuple(shape) + (info.theta.shape[1],):
+                linear = (info.root, role, info.link)
+        elif over_rows and info.theta.dim() == 1 and \
+                info.link == ("exp" if family == "poisson" else "identity") and \
+                all(mode.lookup(p, "matmul") is None for j, p in enumerate(params) if j != role):
+            if role == 1:
+                eligible = "logits" in distribution.__dict__ and not is_batched(params[0])
+            else:
+                eligible = family in ("normal", "bernoulli_logits", "poisson")
+            if eligible:
+                linear = (info.root, role, info.link)
+        gathered = cls._gathered_roles(mode, family, distribution, params, data, shape) \
+            if linear is None else None
+        if gathered is not None:
+            # the other roles: the scalar a broadcast beside the placeholder came from
+            params = [p if g is not None else mode.sources.get(id(p), mode.materialize(p))
+                      for p, g in zip(params, gathered)]
+        else:
+            params = [p if (linear is not None and j == role) else mode.materialize(p)
+                      for j, p in enumerate(params)]
+        if family in ("dirichlet", "mixture_normal"):
+            data = mode.materialize(data)
+        return linear, gathered, params, data
+
     @staticmethod
     def _gathered_roles(mode, family: str, distribution: Distribution, params: List[Any],
                         data: torch.Tensor, shape: torch.Size):
         """
-        Per parameter role the gather placeholder (``linear.DeferredGather``) a gathered site
+        Per parameter role the gather placeholder's record (``linear.Deferred``) a gathered site
         evaluates inside its kernel, or None for a site that is not one: a Normal,
         Bernoulli-logits or Poisson (rate = exp of the predictor) site over an unbatched value of
         shape (N,) whose gathered roles share one index [N] and carry a link the family takes,
         with no deferred matmul among the other roles.
         """
-        infos = [mode.lookup_gather(p) for p in params]
+        infos = [mode.lookup(p, "gather") for p in params]
         if not any(info is not None for info in infos):
             return None
         if family not in ("normal", "bernoulli_logits", "poisson") or \
@@ -682,7 +688,7 @@ class ParticleTracer(TracerMixin):
             return None
         if is_batched(data) or tuple(data.shape) != (N,) or tuple(shape) != (N,):
             return None
-        if any(mode.lookup(p) is not None for p in params):
+        if any(mode.lookup(p, "matmul") is not None for p in params):
             return None
         return infos
 
