@@ -25,6 +25,7 @@
 #include "entropy.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -255,6 +256,29 @@ MI_DEV double block_sum(double v, double* scratch) {
 #pragma unroll
   for (int w = 0; w < kBcastThreads / 64; ++w) out += scratch[w];
   return out;
+}
+
+// N block sums in one barrier round: each by block_sum's tree (the same bits), `scratch` N times
+// as long.
+template <int N, typename T>
+MI_DEV void block_sum_n(T (&v)[N], T* scratch) {
+  constexpr int kWaves = kBcastThreads / 64;
+#pragma unroll
+  for (int j = 0; j < N; ++j) v[j] = wave_sum(v[j]);
+  const int wave = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) scratch[j * kWaves + wave] = v[j];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    T out = (T)0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) out += scratch[j * kWaves + w];
+    v[j] = out;
+  }
 }
 
 // Per-particle constants of a BCAST site, computed once per particle (not once per element chunk):
@@ -577,6 +601,11 @@ typedef const __attribute__((address_space(4))) float smem_float;
 
 // One workgroup of a group's side job (mi_side): the mi_beta_dgrad factors of 256 (draw, component)
 // pairs, one per thread -- latency-bound fp64 chains that run beside the site workgroups.
+// The side job's workgroups, as the plan (make_plan) and the kernel count them.
+__host__ __device__ inline int64_t beta_side_blocks(const mi_side& S) {
+  return S.out != nullptr ? (2 * S.K * S.N + kBcastThreads - 1) / kBcastThreads : 0;
+}
+
 MI_DEV void beta_side_block(const mi_side& S, int64_t b) {
   const int64_t t = b * kBcastThreads + threadIdx.x;
   if (t >= 2 * S.K * S.N) return;
@@ -611,6 +640,35 @@ MI_DEV void beta_side_block(const mi_side& S, int64_t b) {
 // chunk: elements per chunk, a multiple of 32 and at most kSmemMaxChunk (the host sizes it so that
 // chunks x particle blocks fill the chip's workgroup slots: make_plan).
 constexpr int kSmemMaxChunk = 4096;
+
+// The timeline build (tools/c2_timeline.py compiles this file with MI_SITES_TIMELINE defined):
+// thread 0 of every workgroup of k_site_bcast_smem records the constant-rate clock (s_memrealtime,
+// 100 MHz) at entry (0), after the logits (1), after the chunk pass and its barrier round (2),
+// after the last read-out of the first matrix pass (3), after the matrix loop (4), after the
+// chunks' values are stored (5) and at exit (6), into row blockIdx.x of g_tl; word 7 is
+// kind + 2 (particle block + 16 chunk group), kind 1 for a side-job workgroup.
+#ifdef MI_SITES_TIMELINE
+constexpr int kTimelineRows = 8192;
+__device__ unsigned long long g_tl[kTimelineRows * 8];
+#define MI_TL_BEGIN() \
+  unsigned long long tl_[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull}; \
+  tl_[0] = __builtin_amdgcn_s_memrealtime()
+#define MI_TL(i) tl_[i] = __builtin_amdgcn_s_memrealtime()
+#define MI_TL_END(kind, group, kb) \
+  do { \
+    __syncthreads(); \
+    if (threadIdx.x == 0 && blockIdx.x < kTimelineRows) { \
+      unsigned long long* row_ = g_tl + (size_t)blockIdx.x * 8; \
+      for (int i_ = 0; i_ < 6; ++i_) row_[i_] = tl_[i_]; \
+      row_[6] = __builtin_amdgcn_s_memrealtime(); \
+      row_[7] = (unsigned long long)(kind) + 2ull * ((unsigned long long)(kb) + 16ull * (unsigned long long)(group)); \
+    } \
+  } while (0)
+#else
+#define MI_TL_BEGIN() do {} while (0)
+#define MI_TL(i) do {} while (0)
+#define MI_TL_END(kind, group, kb) do {} while (0)
+#endif
 
 // The matrix loop of k_site_bcast_smem (mode bit 3, MININF_AMD_BCAST_MFMA): a chunk whose elements
 // are all exactly 0 or 1 is summed on the bf16 matrix cores with no rounding anywhere.
@@ -655,98 +713,128 @@ MI_DEV void logit_pieces(float l, i32x4 (&b)[3]) {
   }
 }
 
-// sum_i x_i l_k for the kSmemP particles of every lane, from the chunk staged in `xa` as bf16
-// (zeros past its end, up to a whole fragment). `first_k`: the wave's first particle of slot 0.
-template <int kSmemP>
-MI_DEV void bcast_matrix_loop(const __bf16* xa, int nfrag, const f32x2 (&ld)[kSmemP],
-                              double (&acc)[kSmemP], int64_t first_k, int64_t K) {
-  static_assert(kSmemP % kMatrixP == 0, "whole passes");
+// sum_i x_i l_k for the kSmemP particles of every lane, for each of the workgroup's chunks whose bit
+// is set in `mat`: chunk j staged at xa + j kSmemMaxChunk as bf16 (zeros past its end, up to a whole
+// fragment), nfrag(j) >= 1 fragments long. The pieces of a pass are split once and every chunk walks
+// them; a chunk's accumulators are read out before the next chunk starts (each chunk keeps a partial
+// of its own), and `fold(j, p, total)` takes the total of chunk j and particle slot p: slots in
+// order within a chunk. `first_k`: the wave's first particle of slot 0.
+template <int kSmemP, int CPW, int MP, typename Frags, typename Fold>
+MI_DEV void bcast_matrix_loop(const __bf16* xa, uint32_t mat, Frags nfrag,
+                              const f32x2 (&ld)[kSmemP], int64_t first_k, int64_t K, Fold fold) {
+  static_assert(kSmemP % MP == 0, "whole passes");
   const int lane = threadIdx.x & 63;
   const int col = lane & 15, grp = lane >> 4;
-  const i32x4* frag = reinterpret_cast<const i32x4*>(xa) + lane;
 #pragma unroll
-  for (int p0 = 0; p0 < kSmemP; p0 += kMatrixP) {
+  for (int p0 = 0; p0 < kSmemP; p0 += MP) {
     // (wave-uniform: a pass none of whose particles exist is skipped; its lanes store nothing)
     if (first_k + (int64_t)p0 * kBcastThreads >= K) continue;
-    i32x4 b[kMatrixP][4][3];
-    f32x4 d[kMatrixP][4][3];
+    i32x4 b[MP][4][3];
 #pragma unroll
-    for (int pp = 0; pp < kMatrixP; ++pp)
+    for (int pp = 0; pp < MP; ++pp)
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        logit_pieces(__shfl(ld[p0 + pp].x, g * 16 + col, 64), b[pp][g]);
+      for (int g = 0; g < 4; ++g) logit_pieces(__shfl(ld[p0 + pp].x, g * 16 + col, 64), b[pp][g]);
+    // (not unrolled: one copy of the loop, and the registers of one chunk, whatever CPW is)
+#pragma unroll 1
+    for (int j = 0; j < CPW; ++j) {
+      if (((mat >> j) & 1u) == 0u) continue;   // (uniform over the workgroup)
+      const i32x4* frag = reinterpret_cast<const i32x4*>(xa + j * kSmemMaxChunk) + lane;
+      const int nf = nfrag(j);
+      f32x4 d[MP][4][3];
 #pragma unroll
-        for (int q = 0; q < 3; ++q) d[pp][g][q] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-      }
-    // The loop is written out: from the builtin the compiler routes half the accumulators through
-    // a scratch tile, four register moves and a wait per instruction. Accumulators are tied in
-    // AGPRs, fragments stay in VGPRs; between two instructions on one accumulator stand 23 others.
-    // The compiler's hazard recogniser does not see inside the assembly: after a toolchain change
-    // read the ISA of this loop again (the accumulators' zeroing before the first instruction,
-    // the s_waitcnt before the fragment's first use, the waits after the loop).
-    int f = 0;
-    i32x4 next = frag[0];
-    do {   // (nfrag >= 1: a chunk is never empty. The next fragment's read is issued ahead of
-           // this fragment's 24 instructions and waited for behind them: one iteration of overlap,
-           // not a second buffer.)
-      const i32x4 a = next;
-      next = frag[min(f + 1, nfrag - 1) * (kFragElems / 8)];
-#pragma unroll
-      for (int pp = 0; pp < kMatrixP; ++pp)
+      for (int pp = 0; pp < MP; ++pp)
 #pragma unroll
         for (int g = 0; g < 4; ++g)
 #pragma unroll
-          for (int q = 0; q < 3; ++q)
-            __asm__ volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0"
-                             : "+a"(d[pp][g][q]) : "v"(a), "v"(b[pp][g][q]));
-    } while (++f < nfrag);
-    // v_mfma_f32_16x16x32_bf16 is an 8-pass instruction, and a VALU read of a matrix result
-    // has to stand passes + 3 = 11 wait states behind it (19 behind a 16-pass one; the compiler's
-    // hazard table for gfx950). Each statement below waits 32 (two s_nop 15); there are kMatrixP
-    // of them, in order, each tied to half the accumulators.
+          for (int q = 0; q < 3; ++q) d[pp][g][q] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      // The loop is written out: from the builtin the compiler routes half the accumulators through
+      // a scratch tile, four register moves and a wait per instruction. Accumulators are tied in
+      // AGPRs, fragments stay in VGPRs; between two instructions on one accumulator stand 23 others.
+      // The compiler's hazard recogniser does not see inside the assembly: after a toolchain change
+      // read the ISA of this loop again (the accumulators' zeroing before the first instruction,
+      // the s_waitcnt before the fragment's first use, the waits after the loop).
+      int f = 0;
+      i32x4 next = frag[0];
+      do {   // (nf >= 1: a chunk is never empty. The next fragment's read is issued ahead of
+             // this fragment's 24 instructions and waited for behind them: one iteration of overlap,
+             // not a second buffer.)
+        const i32x4 a = next;
+        next = frag[min(f + 1, nf - 1) * (kFragElems / 8)];
 #pragma unroll
-    for (int pp = 0; pp < kMatrixP; ++pp)
-      __asm__ volatile("s_nop 15\n\ts_nop 15"
-                       : "+a"(d[pp][0][0]), "+a"(d[pp][0][1]), "+a"(d[pp][0][2]), "+a"(d[pp][1][0]),
-                         "+a"(d[pp][1][1]), "+a"(d[pp][1][2]), "+a"(d[pp][2][0]), "+a"(d[pp][2][1]),
-                         "+a"(d[pp][2][2]), "+a"(d[pp][3][0]), "+a"(d[pp][3][1]), "+a"(d[pp][3][2]));
-    // D's rows: four registers, then the four lane groups. Lane group g keeps tile g (its lanes
-    // own that tile's particles), so the groups trade halves instead of all summing every tile.
-    // (fp32, exact: count x piece.)
+        for (int pp = 0; pp < MP; ++pp)
 #pragma unroll
-    for (int pp = 0; pp < kMatrixP; ++pp) {
-      double total = 0.0;
+          for (int g = 0; g < 4; ++g)
 #pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        float v[4];
+            for (int q = 0; q < 3; ++q)
+              __asm__ volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0"
+                               : "+a"(d[pp][g][q]) : "v"(a), "v"(b[pp][g][q]));
+      } while (++f < nf);
+      // v_mfma_f32_16x16x32_bf16 is an 8-pass instruction, and a VALU read of a matrix result
+      // has to stand passes + 3 = 11 wait states behind it (19 behind a 16-pass one; the compiler's
+      // hazard table for gfx950). Each statement below waits 32 (two s_nop 15); there are MP
+      // of them, in order, each tied to half the accumulators. They stand before every read-out:
+      // once per chunk and pass.
 #pragma unroll
-        for (int g = 0; g < 4; ++g)
-          v[g] = (d[pp][g][q].x + d[pp][g][q].y) + (d[pp][g][q].z + d[pp][g][q].w);
-        const bool hi = grp >= 2, odd = (grp & 1) != 0;
-        const float w0 = (hi ? v[2] : v[0]) + __shfl_xor(hi ? v[0] : v[2], 32, 64);
-        const float w1 = (hi ? v[3] : v[1]) + __shfl_xor(hi ? v[1] : v[3], 32, 64);
-        const float t = (odd ? w1 : w0) + __shfl_xor(odd ? w0 : w1, 16, 64);
-        total += (double)t;
+      for (int pp = 0; pp < MP; ++pp)
+        __asm__ volatile("s_nop 15\n\ts_nop 15"
+                         : "+a"(d[pp][0][0]), "+a"(d[pp][0][1]), "+a"(d[pp][0][2]), "+a"(d[pp][1][0]),
+                           "+a"(d[pp][1][1]), "+a"(d[pp][1][2]), "+a"(d[pp][2][0]), "+a"(d[pp][2][1]),
+                           "+a"(d[pp][2][2]), "+a"(d[pp][3][0]), "+a"(d[pp][3][1]), "+a"(d[pp][3][2]));
+      // D's rows: four registers, then the four lane groups. Lane group g keeps tile g (its lanes
+      // own that tile's particles), so the groups trade halves instead of all summing every tile.
+      // (fp32, exact: count x piece.)
+#pragma unroll
+      for (int pp = 0; pp < MP; ++pp) {
+        double total = 0.0;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          float v[4];
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            v[g] = (d[pp][g][q].x + d[pp][g][q].y) + (d[pp][g][q].z + d[pp][g][q].w);
+          }
+          const bool hi = grp >= 2, odd = (grp & 1) != 0;
+          const float w0 = (hi ? v[2] : v[0]) + __shfl_xor(hi ? v[0] : v[2], 32, 64);
+          const float w1 = (hi ? v[3] : v[1]) + __shfl_xor(hi ? v[1] : v[3], 32, 64);
+          const float t = (odd ? w1 : w0) + __shfl_xor(odd ? w0 : w1, 16, 64);
+          total += (double)t;
+        }
+        fold(j, p0 + pp, total);
       }
-      acc[p0 + pp] = total;
     }
   }
 }
 
-// MATRIX: the instantiation that holds the matrix loop (236 / 232 registers with 96 AGPRs and 8 KB
-// of LDS: two waves per SIMD). Without it the kernel is the scalar-load loop alone, at its 78
+// MATRIX: the instantiation that holds the matrix loop (240 / 236 registers with 96 AGPRs and 8 KB
+// of LDS: two waves per SIMD). Without it the kernel is the scalar-load loop alone, at its 90
 // registers and four workgroups per CU: what MININF_AMD_BCAST_MFMA=0 launches.
-template <int FAMILY, int kSmemP, bool SUFF = false, bool MATRIX = false>
+// (CPW = 2 / 4: one particle slot per matrix pass, 152 / 160 registers with 48 AGPRs, 20 / 40 KB
+// of LDS, no scratch: three waves per SIMD.)
+// CPW (chunks per workgroup, the matrix instantiation only; MININF_AMD_BCAST_CPW): the workgroup
+// owns particle block `kblock` and the CPW consecutive chunks of chunk group g, [g CPW, min((g + 1)
+// CPW, chunks)). The chunk plan, every partial and every index written are those of CPW = 1; what
+// is paid once per workgroup instead of once per chunk is the setup (arguments, parameters, logits),
+// the latency of the chunk pass (all the group's loads are in flight together), one barrier round
+// for all the chunk sums and flags, the piece splits of a pass and the slot epilogue. launch_smem
+// picks CPW so that the grid fits one round of resident workgroups. With CPW > 1 the side job's
+// workgroups (padded to a multiple of 8: the XCD mapping stays) come first in the grid.
+template <int FAMILY, int kSmemP, bool SUFF = false, bool MATRIX = false, int CPW = 1>
 __global__ __launch_bounds__(kBcastThreads) void k_site_bcast_smem(const mi_group G,
                                                                    float* __restrict__ part,
                                                                    int64_t nseg, int gy,
                                                                    int mode, int chunk,
                                                                    uint32_t* __restrict__ flags,
                                                                    double* __restrict__ ksum) {
-  __shared__ float scratch[kBcastThreads / 64];
-  __shared__ double dscratch[kBcastThreads / 64];
-  __shared__ __attribute__((aligned(16))) __bf16 xa[MATRIX ? kSmemMaxChunk : 8];   // the matrix loop's chunk
+  static_assert(CPW == 1 || (MATRIX && !SUFF), "several chunks per workgroup: the matrix loop only");
+  static_assert(CPW >= 1 && CPW <= 4, "the staged chunks: at most 32 KB of LDS");
+  constexpr int kWaves = kBcastThreads / 64;
+  __shared__ float scratch[CPW * kWaves];
+  __shared__ double dscratch[CPW * kWaves];
+  __shared__ uint32_t other_of_wave[kWaves];
+  __shared__ double lane_sum[CPW > 1 ? CPW * kBcastThreads : 1];   // (below: the matrix loop's fold)
+  __shared__ __attribute__((aligned(16))) __bf16 xa[MATRIX ? CPW * kSmemMaxChunk : 8];   // the matrix loop's chunks
   kernarg_prefetch<(int)sizeof(mi_group)>();
+  MI_TL_BEGIN();
   // mode bit 0: rank-one slot layout; bit 1: progress-balanced wave priority (below); bit 2:
   // particle-summed values
   const int rank1 = mode & 1;
@@ -754,22 +842,37 @@ __global__ __launch_bounds__(kBcastThreads) void k_site_bcast_smem(const mi_grou
   const bool ksummed = (mode & 4) != 0;
   constexpr bool try_matrix = MATRIX && !SUFF;
   const int64_t chunks = nseg - 1;
-  const int64_t padded = (chunks + 7) / 8 * 8;
-  const int64_t b = blockIdx.x;
-  if (b >= padded * gy) {   // workgroups past the chunks: the side job (mi_side)
+  const int64_t groups = (chunks + CPW - 1) / CPW;
+  const int64_t padded = (groups + 7) / 8 * 8;
+  int64_t b = blockIdx.x;
+  // The side job (mi_side): the workgroups past the chunks, or (CPW > 1) those before them, so that
+  // they start with the launch and the main workgroups that wait for their slots start within the
+  // side job's length.
+  // (their number from the arguments, as make_plan counts them: gridDim is a load from a line of
+  // the argument segment that nothing has prefetched, in front of every workgroup)
+  const int64_t side = (beta_side_blocks(G.side) + 7) / 8 * 8;
+  if (CPW == 1 ? b >= padded * gy : b < side) {
     const unsigned long long ts = span_begin(G.stamps);   // (the launch's span includes them)
-    beta_side_block(G.side, b - padded * gy);
+    beta_side_block(G.side, CPW == 1 ? b - padded * gy : b);   // (padding: past the job's end)
     span_end(G.stamps, ts);
+    MI_TL_END(1, 0, 0);
     return;
   }
-  const int64_t c = (b / (8 * gy)) * 8 + b % 8;
+  if (CPW > 1) b -= side;
+  const int64_t g = (b / (8 * gy)) * 8 + b % 8;
   const int64_t kblock = (b / 8) % gy;
-  if (c >= chunks) return;   // padding
+  if (g >= groups) return;   // padding
   const unsigned long long t0 = span_begin(G.stamps);
   const mi_site& st = G.sites[0];
   const float* xg = G.operands[st.operand[2]].data;
-  const int64_t i0 = c * chunk;
-  const int len = (int)min((int64_t)chunk, G.N - i0);
+  const int64_t c0 = g * CPW;   // the workgroup's chunks: c0 + j, j < nc
+  const int nc = (int)min((int64_t)CPW, chunks - c0);
+  // (pinned: a reload of N inside the matrix loop would be a scalar load among its LDS reads, and
+  // the fragment prefetch would then be waited for at once)
+  const int64_t left = CPW > 1 ? pin(G.N - c0 * chunk) : G.N - c0 * chunk;
+  auto chunk_len = [&](int j) -> int {
+    return j < nc ? (int)min((int64_t)chunk, left - (int64_t)j * chunk) : 0;
+  };
   uint32_t fl = 0u;
 
   // ---- per-particle logits (as k_bcast_prep) ---------------------------------------------------
@@ -795,115 +898,231 @@ __global__ __launch_bounds__(kBcastThreads) void k_site_bcast_smem(const mi_grou
     float l, d;
     const bool bad = logits(p, l, d);
     ld[p] = f32x2{l, l};
-    fl |= (c == 0 && kbase + p * kBcastThreads < K && bad) ? MI_FLAG_PARAM : 0u;
+    fl |= (g == 0 && kbase + p * kBcastThreads < K && bad) ? MI_FLAG_PARAM : 0u;
   }
+  MI_TL(1);
 
-  // ---- sum_i x_i l_k: element pairs from SGPRs against duplicated particle logits --------------
-  double acc[kSmemP];
-#pragma unroll
-  for (int p = 0; p < kSmemP; ++p) acc[p] = 0.0;
-
-  // ---- chunk sum and support flags (vector loads) ----------------------------------------------
-  // Each lane takes kSmemMaxChunk / kBcastThreads consecutive elements (those within the chunk)
-  // with all its loads in flight at once (a strided loop waits for one L2 round trip per element
-  // group, at the end of every wave). STAGE: the lane's elements also go to `xa` as bf16, zeros
-  // past the chunk's end.
+  // ---- chunk sums and support flags (vector loads) ---------------------------------------------
+  // Each lane takes kSmemMaxChunk / kBcastThreads consecutive elements of every chunk (those within
+  // it) with all its loads, of all the workgroup's chunks, in flight at once (a strided loop waits
+  // for one L2 round trip per element group, at the end of every wave). STAGE: the lane's elements
+  // also go to `xa` as bf16, zeros past the chunk's end. A chunk's sum adds the lane's elements in
+  // order from 0, then block_sum's tree: the same bits whatever CPW is.
   constexpr int kPerLane = kSmemMaxChunk / kBcastThreads;
   static_assert(kPerLane % 8 == 0, "whole float4 groups, and whole 16-byte bf16 groups, per lane");
-  float s_a = 0.0f;
+  float s_a[CPW];
+  uint32_t other = 0u;   // bit j: one of this lane's elements of chunk j is neither 0 nor 1
   auto chunk_pass = [&](auto stage_tag) {
     constexpr bool STAGE = decltype(stage_tag)::value && MATRIX;
     const int e0 = (int)threadIdx.x * kPerLane;
-    const float* xl = xg + i0 + e0;
-    float v[kPerLane];
-    if (e0 + kPerLane <= len && (reinterpret_cast<uintptr_t>(xl) & 15) == 0) {
+    float4 t[CPW][kPerLane / 4];
+    bool whole[CPW];
 #pragma unroll
-      for (int q = 0; q < kPerLane / 4; ++q) {
-        const float4 t = reinterpret_cast<const float4*>(xl)[q];
-        v[4 * q] = t.x;
-        v[4 * q + 1] = t.y;
-        v[4 * q + 2] = t.z;
-        v[4 * q + 3] = t.w;
-      }
+    for (int j = 0; j < CPW; ++j) {
+      const float* xl = xg + (c0 + j) * chunk + e0;
+      whole[j] = e0 + kPerLane <= chunk_len(j) && (reinterpret_cast<uintptr_t>(xl) & 15) == 0;
+      if (whole[j]) {
 #pragma unroll
-      for (int e = 0; e < kPerLane; ++e) {
-        fl |= !(v[e] == 0.0f || v[e] == 1.0f) ? MI_FLAG_SUPPORT : 0u;
-        s_a += v[e];
+        for (int q = 0; q < kPerLane / 4; ++q) t[j][q] = reinterpret_cast<const float4*>(xl)[q];
       }
-    } else {
-#pragma unroll 1
-      for (int e = e0; e < len && e < e0 + kPerLane; ++e) {
-        const float t = xg[i0 + e];
-        fl |= !(t == 0.0f || t == 1.0f) ? MI_FLAG_SUPPORT : 0u;
-        s_a += t;
-        if (STAGE) xa[e] = (__bf16)t;
-      }
-      if (STAGE)
-        for (int e = max(e0, len); e < e0 + kPerLane; ++e) xa[e] = (__bf16)0.0f;
-      return;
     }
-    if (STAGE) {
 #pragma unroll
-      for (int q = 0; q < kPerLane / 8; ++q) {
-        bf16x8 t;
+    for (int j = 0; j < CPW; ++j) {
+      const int len = chunk_len(j);
+      __bf16* xj = xa + (STAGE ? j * kSmemMaxChunk : 0);
+      float s = 0.0f;
+      bool bad = false;
+      if (whole[j]) {
+        float v[kPerLane];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) t[e] = (__bf16)v[8 * q + e];
-        reinterpret_cast<bf16x8*>(xa + e0)[q] = t;
+        for (int q = 0; q < kPerLane / 4; ++q) {
+          v[4 * q] = t[j][q].x;
+          v[4 * q + 1] = t[j][q].y;
+          v[4 * q + 2] = t[j][q].z;
+          v[4 * q + 3] = t[j][q].w;
+        }
+#pragma unroll
+        for (int e = 0; e < kPerLane; ++e) {
+          bad |= !(v[e] == 0.0f || v[e] == 1.0f);
+          s += v[e];
+        }
+        if (STAGE) {
+#pragma unroll
+          for (int q = 0; q < kPerLane / 8; ++q) {
+            bf16x8 h;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) h[e] = (__bf16)v[8 * q + e];
+            reinterpret_cast<bf16x8*>(xj + e0)[q] = h;
+          }
+        }
+      } else if (j < nc) {
+        const float* xc = xg + (c0 + j) * chunk;
+#pragma unroll 1
+        for (int e = e0; e < len && e < e0 + kPerLane; ++e) {
+          const float x = xc[e];
+          bad |= !(x == 0.0f || x == 1.0f);
+          s += x;
+          if (STAGE) xj[e] = (__bf16)x;
+        }
+        if (STAGE)
+          for (int e = max(e0, len); e < e0 + kPerLane; ++e) xj[e] = (__bf16)0.0f;
       }
+      s_a[j] = s;
+      other |= bad ? 1u << j : 0u;
+    }
+    fl |= other != 0u ? MI_FLAG_SUPPORT : 0u;
+  };
+
+  // ---- partials of a chunk's site value ------------------------------------------------------
+  const int64_t first_k = kblock * (kBcastThreads * kSmemP) + (threadIdx.x & ~63);
+  auto store_values = [&](int64_t c, const double (&acc)[kSmemP]) {
+    double vsum = 0.0;
+#pragma unroll
+    for (int p = 0; p < kSmemP; ++p) {
+      const int64_t k = kbase + p * kBcastThreads;
+      if (k >= K) continue;
+      if (ksummed) vsum += acc[p];
+      else part[c * K + k] = (float)acc[p];
+    }
+    if (ksummed) {
+      vsum = block_sum(vsum, dscratch);
+      if (threadIdx.x == 0) ksum[c * gy + kblock] = vsum;
     }
   };
-  // The matrix loop needs the whole chunk to be 0/1, so with it enabled the pass runs first: it
-  // stages the chunk, and the workgroup agrees on the answer (wave-uniform, no host round trip).
-  bool matrix = false;
+
+  // The matrix loop needs a whole chunk to be 0/1, so with it enabled the pass runs first: it
+  // stages the chunks, and the workgroup agrees on the answer for each of them in one barrier round
+  // (the chunk sums' round; wave-uniform, no host round trip).
+  uint32_t scalar_chunks = (1u << nc) - 1u;   // bit j: chunk j takes the scalar-load loop
   if constexpr (try_matrix) {
     chunk_pass(std::true_type{});
-    s_a = block_sum(s_a, scratch);
-    matrix = __syncthreads_or((fl & MI_FLAG_SUPPORT) != 0u ? 1 : 0) == 0;
-  }
-  if constexpr (try_matrix)
-    if (matrix)
-      bcast_matrix_loop<kSmemP>(xa, (len + kFragElems - 1) / kFragElems, ld, acc,
-                                kblock * (kBcastThreads * kSmemP) + (threadIdx.x & ~63), K);
-
-  // (a chunk with any other value, and every chunk with the matrix loop off: the scalar-load loop)
-  const int vlen = matrix ? 0 : len;
-  smem_float* xs = (smem_float*)(xg + i0);
-  auto flush = [&](const f32x2 (&in)[2][kSmemP]) {
+    uint32_t any = other;
 #pragma unroll
-    for (int p = 0; p < kSmemP; ++p)
-      acc[p] += (double)((in[0][p].x + in[0][p].y) + (in[1][p].x + in[1][p].y));
-  };
-  // Whole 256-element blocks in groups of 32 (two s_load_dwordx16): the next group's loads are in
-  // flight during this group's packed FMAs (scalar loads return out of order, so every use waits
-  // for all of them: one group of lookahead). Even and odd element pairs go to separate
-  // accumulators, 2 kSmemP independent chains of 64 terms per block.
-  constexpr int kGroup = 32, kBlock = 256;
-  const int nfull = SUFF ? 0 : vlen & ~(kBlock - 1);
-  int j = 0;
-  if (nfull > 0) {
-    float xc[kGroup];
+    for (int offset = 32; offset > 0; offset >>= 1) any |= __shfl_xor(any, offset, kWave);
+    if ((threadIdx.x & 63) == 0) other_of_wave[threadIdx.x >> 6] = any;
+    block_sum_n<CPW>(s_a, scratch);   // (its barriers publish other_of_wave and the staged chunks)
+    any = 0u;
 #pragma unroll
-    for (int e = 0; e < kGroup; ++e) xc[e] = xs[e];
-    // the first block index of each later quarter of the chunk (no division inside the loop)
-    const int q1 = (nfull / 4 + kBlock - 1) & ~(kBlock - 1), q2 = (nfull / 2 + kBlock - 1) & ~(kBlock - 1),
-              q3 = (3 * nfull / 4 + kBlock - 1) & ~(kBlock - 1);
-    if (balance) __builtin_amdgcn_s_setprio(3);
-    for (; j < nfull; j += kBlock) {
-      // Progress-balanced priority: a wave drops one priority level per quarter of its chunk, so
-      // the SIMD's arbiter (priority, then age) lets the waves behind it catch up; the waves of a
-      // SIMD then finish together instead of the oldest first, which would leave the last one
-      // issuing alone (at half the VALU rate) through the kernel's tail.
-      if (balance) {
-        if (j == q1) __builtin_amdgcn_s_setprio(2);
-        else if (j == q2) __builtin_amdgcn_s_setprio(1);
-        else if (j == q3) __builtin_amdgcn_s_setprio(0);
+    for (int w = 0; w < kWaves; ++w) any |= other_of_wave[w];
+    scalar_chunks &= any;
+    MI_TL(2);
+    const uint32_t mat = ((1u << nc) - 1u) & ~any;
+    if (mat != 0u) {
+      // A chunk's particle sum in the present order: slots 0, 1 from the first pass, 2, 3 from the
+      // second, from 0.0, lanes past K adding nothing. No per-slot totals live through the loop:
+      // the lane's running sum of chunk j is a register (CPW = 1) or its own LDS word.
+      // Particle slots per pass: kMatrixP, or one where the pieces have to stay live through a
+      // chunk's read-out for the next chunk (CPW > 1: 48 + 48 registers a pass instead of 96 + 96,
+      // the chunk read from LDS four times instead of twice).
+      constexpr int kPassP = CPW > 1 ? 1 : kMatrixP;
+      double vsum[CPW];
+#pragma unroll
+      for (int j = 0; j < CPW; ++j) vsum[j] = 0.0;
+      if constexpr (CPW > 1) {
+#pragma unroll
+        for (int j = 0; j < CPW; ++j) lane_sum[j * kBcastThreads + threadIdx.x] = 0.0;
       }
+      bcast_matrix_loop<kSmemP, CPW, kPassP>(
+          xa, mat, [&](int j) { return (chunk_len(j) + kFragElems - 1) / kFragElems; }, ld, first_k, K,
+          [&](int j, int p, double total) {
+            const int64_t k = kbase + p * kBcastThreads;
+            if (p == kPassP - 1) MI_TL(3);
+            if (k >= K) return;
+            if (!ksummed) part[(c0 + j) * K + k] = (float)total;
+            else if constexpr (CPW == 1) vsum[0] += total;
+            else lane_sum[j * kBcastThreads + threadIdx.x] += total;
+          });
+      MI_TL(4);
+      if (ksummed) {
+        if constexpr (CPW > 1) {
+#pragma unroll
+          for (int j = 0; j < CPW; ++j) vsum[j] = lane_sum[j * kBcastThreads + threadIdx.x];
+        }
+        block_sum_n<CPW>(vsum, dscratch);
+        if (threadIdx.x == 0) {
+#pragma unroll
+          for (int j = 0; j < CPW; ++j)
+            if ((mat >> j) & 1u) ksum[(c0 + j) * gy + kblock] = vsum[j];
+        }
+      }
+    }
+  }
+  MI_TL(5);
+
+  // ---- sum_i x_i l_k: element pairs from SGPRs against duplicated particle logits --------------
+  // (a chunk with any other value, and every chunk with the matrix loop off: the scalar-load loop,
+  // one chunk at a time)
+#pragma unroll 1
+  for (int cj = 0; cj < (try_matrix ? nc : 1); ++cj) {
+    if constexpr (try_matrix)
+      if (((scalar_chunks >> cj) & 1u) == 0u) continue;
+    double acc[kSmemP];
+#pragma unroll
+    for (int p = 0; p < kSmemP; ++p) acc[p] = 0.0;
+    const int64_t i0 = (c0 + cj) * chunk;
+    const int vlen = chunk_len(cj);
+    smem_float* xs = (smem_float*)(xg + i0);
+    auto flush = [&](const f32x2 (&in)[2][kSmemP]) {
+#pragma unroll
+      for (int p = 0; p < kSmemP; ++p)
+        acc[p] += (double)((in[0][p].x + in[0][p].y) + (in[1][p].x + in[1][p].y));
+    };
+    // Whole 256-element blocks in groups of 32 (two s_load_dwordx16): the next group's loads are in
+    // flight during this group's packed FMAs (scalar loads return out of order, so every use waits
+    // for all of them: one group of lookahead). Even and odd element pairs go to separate
+    // accumulators, 2 kSmemP independent chains of 64 terms per block.
+    constexpr int kGroup = 32, kBlock = 256;
+    const int nfull = SUFF ? 0 : vlen & ~(kBlock - 1);
+    int j = 0;
+    if (nfull > 0) {
+      float xc[kGroup];
+#pragma unroll
+      for (int e = 0; e < kGroup; ++e) xc[e] = xs[e];
+      // the first block index of each later quarter of the chunk (no division inside the loop)
+      const int q1 = (nfull / 4 + kBlock - 1) & ~(kBlock - 1), q2 = (nfull / 2 + kBlock - 1) & ~(kBlock - 1),
+                q3 = (3 * nfull / 4 + kBlock - 1) & ~(kBlock - 1);
+      if (balance) __builtin_amdgcn_s_setprio(3);
+      for (; j < nfull; j += kBlock) {
+        // Progress-balanced priority: a wave drops one priority level per quarter of its chunk, so
+        // the SIMD's arbiter (priority, then age) lets the waves behind it catch up; the waves of a
+        // SIMD then finish together instead of the oldest first, which would leave the last one
+        // issuing alone (at half the VALU rate) through the kernel's tail.
+        if (balance) {
+          if (j == q1) __builtin_amdgcn_s_setprio(2);
+          else if (j == q2) __builtin_amdgcn_s_setprio(1);
+          else if (j == q3) __builtin_amdgcn_s_setprio(0);
+        }
+        f32x2 in[2][kSmemP];
+#pragma unroll
+        for (int p = 0; p < kSmemP; ++p) in[0][p] = in[1][p] = f32x2{0.0f, 0.0f};
+#pragma unroll
+        for (int g = 0; g < kBlock; g += kGroup) {
+          const int nxt = min(j + g + kGroup, nfull - kGroup);   // in bounds; the last is unused
+          float xn[kGroup];
+#pragma unroll
+          for (int e = 0; e < kGroup; ++e) xn[e] = xs[nxt + e];
+#pragma unroll
+          for (int e = 0; e < kGroup; e += 2) {
+            const f32x2 xv = f32x2{xc[e], xc[e + 1]};
+#pragma unroll
+            for (int p = 0; p < kSmemP; ++p)
+              in[(e >> 1) & 1][p] = __builtin_elementwise_fma(xv, ld[p], in[(e >> 1) & 1][p]);
+          }
+#pragma unroll
+          for (int e = 0; e < kGroup; ++e) xc[e] = xn[e];
+        }
+        flush(in);
+      }
+    }
+    if (!SUFF && j + kGroup <= vlen) {   // whole groups of 32 past the last whole block
       f32x2 in[2][kSmemP];
 #pragma unroll
       for (int p = 0; p < kSmemP; ++p) in[0][p] = in[1][p] = f32x2{0.0f, 0.0f};
+      float xc[kGroup];
 #pragma unroll
-      for (int g = 0; g < kBlock; g += kGroup) {
-        const int nxt = min(j + g + kGroup, nfull - kGroup);   // in bounds; the last is unused
+      for (int e = 0; e < kGroup; ++e) xc[e] = xs[j + e];
+      for (; j + kGroup <= vlen; j += kGroup) {
+        const int nxt = min(j + kGroup, vlen - kGroup);   // in bounds; the last is unused
         float xn[kGroup];
 #pragma unroll
         for (int e = 0; e < kGroup; ++e) xn[e] = xs[nxt + e];
@@ -919,52 +1138,29 @@ __global__ __launch_bounds__(kBcastThreads) void k_site_bcast_smem(const mi_grou
       }
       flush(in);
     }
-  }
-  if (!SUFF && j + kGroup <= vlen) {   // whole groups of 32 past the last whole block
-    f32x2 in[2][kSmemP];
+    if (!SUFF && j < vlen) {   // the chunk's tail: element pairs, a zero for an odd last element
+      f32x2 in[2][kSmemP];
 #pragma unroll
-    for (int p = 0; p < kSmemP; ++p) in[0][p] = in[1][p] = f32x2{0.0f, 0.0f};
-    float xc[kGroup];
-#pragma unroll
-    for (int e = 0; e < kGroup; ++e) xc[e] = xs[j + e];
-    for (; j + kGroup <= vlen; j += kGroup) {
-      const int nxt = min(j + kGroup, vlen - kGroup);   // in bounds; the last is unused
-      float xn[kGroup];
-#pragma unroll
-      for (int e = 0; e < kGroup; ++e) xn[e] = xs[nxt + e];
-#pragma unroll
-      for (int e = 0; e < kGroup; e += 2) {
-        const f32x2 xv = f32x2{xc[e], xc[e + 1]};
+      for (int p = 0; p < kSmemP; ++p) in[0][p] = in[1][p] = f32x2{0.0f, 0.0f};
+      for (int e = 0; j < vlen; j += 2, ++e) {
+        const f32x2 xv = f32x2{xs[j], j + 1 < vlen ? xs[j + 1] : 0.0f};
 #pragma unroll
         for (int p = 0; p < kSmemP; ++p)
-          in[(e >> 1) & 1][p] = __builtin_elementwise_fma(xv, ld[p], in[(e >> 1) & 1][p]);
+          in[e & 1][p] = __builtin_elementwise_fma(xv, ld[p], in[e & 1][p]);
       }
-#pragma unroll
-      for (int e = 0; e < kGroup; ++e) xc[e] = xn[e];
+      flush(in);
     }
-    flush(in);
-  }
-  if (!SUFF && j < vlen) {   // the chunk's tail: element pairs, a zero for an odd last element
-    f32x2 in[2][kSmemP];
-#pragma unroll
-    for (int p = 0; p < kSmemP; ++p) in[0][p] = in[1][p] = f32x2{0.0f, 0.0f};
-    for (int e = 0; j < vlen; j += 2, ++e) {
-      const f32x2 xv = f32x2{xs[j], j + 1 < vlen ? xs[j + 1] : 0.0f};
-#pragma unroll
-      for (int p = 0; p < kSmemP; ++p)
-        in[e & 1][p] = __builtin_elementwise_fma(xv, ld[p], in[e & 1][p]);
-    }
-    flush(in);
-  }
 
-  // (without the matrix loop the pass runs here, where the chunk is L2-resident)
-  if (!try_matrix) {
-    chunk_pass(std::false_type{});
-    s_a = block_sum(s_a, scratch);
-  }
-  if (SUFF) {
+    // (without the matrix loop the pass runs here, where the chunk is L2-resident)
+    if (!try_matrix) {
+      chunk_pass(std::false_type{});
+      s_a[0] = block_sum(s_a[0], scratch);
+    }
+    if (SUFF) {
 #pragma unroll
-    for (int p = 0; p < kSmemP; ++p) acc[p] = (double)ld[p].x * (double)s_a;
+      for (int p = 0; p < kSmemP; ++p) acc[p] = (double)ld[p].x * (double)s_a[0];
+    }
+    store_values(c0 + cj, acc);
   }
   __asm__ volatile("" ::: "memory");   // (the parameters are read again, not held in registers)
   float dl[kSmemP];
@@ -982,71 +1178,79 @@ __global__ __launch_bounds__(kBcastThreads) void k_site_bcast_smem(const mi_grou
   const int64_t extra = nseg - 1;
   uint32_t fl_prior = 0u;
   float* slot_part = part + (int64_t)((ksummed ? 0 : 1) + slot_a) * nseg * K;   // (slot_a >= 0)
-  if (rank1 && slot_a >= 0 && kblock == 0 && threadIdx.x == 0) slot_part[c] = s_a;   // u[c]
-  double vsum = 0.0;
 #pragma unroll
-  for (int p = 0; p < kSmemP; ++p) {
-    const int64_t k = kbase + p * kBcastThreads;
-    if (k >= K) continue;
-    if (ksummed) vsum += acc[p];
-    else part[c * K + k] = (float)acc[p];
-    if (slot_a >= 0 && !rank1) slot_part[c * K + k] = w * (s_a * dl[p]);
+  for (int j = 0; j < CPW; ++j) {
+    if (j >= nc) break;
+    const int64_t c = c0 + j;
+    if (rank1 && slot_a >= 0 && kblock == 0 && threadIdx.x == 0) slot_part[c] = s_a[j];   // u[c]
+#pragma unroll
+    for (int p = 0; p < kSmemP; ++p) {
+      const int64_t k = kbase + p * kBcastThreads;
+      if (k >= K) continue;
+      if (slot_a >= 0 && !rank1) slot_part[c * K + k] = w * (s_a[j] * dl[p]);
+    }
   }
-  if (ksummed) {
-    vsum = block_sum(vsum, dscratch);
-    if (threadIdx.x == 0) ksum[c * gy + kblock] = vsum;
-  }
-  // The particle-constant segment: particle slot p of every lane by the chunk-p workgroups (chunk 0
-  // takes all of them when the grid has fewer chunks than particles per lane), one particle at a
-  // time -- the prior's special functions interleaved over the particles held ~40 registers.
+  // The particle-constant segment: particle slot p of every lane by the workgroups of chunk group p
+  // (group 0 takes all of them when the grid has fewer groups than particles per lane), one
+  // particle at a time -- the prior's special functions interleaved over the particles held ~40
+  // registers. The particle sums keep the layout of CPW = 1: one double per slot from four chunks
+  // on (`spread`), one for all slots below that.
   const bool spread = chunks >= kSmemP;
-  if (spread ? c < kSmemP : c == 0) {
-    const int p0 = spread ? (int)c : 0, p1 = spread ? (int)c + 1 : kSmemP;
+  const bool dealt = groups >= kSmemP;
+  if (dealt ? g < kSmemP : g == 0) {
+    const int p0 = dealt ? (int)g : 0, p1 = dealt ? (int)g + 1 : kSmemP;
     double csum = 0.0;
 #pragma unroll 1
     for (int p = p0; p < p1; ++p) {
       const int64_t k = kbase + p * kBcastThreads;
-      if (k >= K) continue;
-      float l, dlp;
-      (void)logits(p, l, dlp);
-      const float t = expf(-fabsf(l));
-      const double softplus = (double)(fmaxf(l, 0.0f) + log1pf(t));
-      const double sig = (double)(l >= 0.0f ? 1.0f / (1.0f + t) : t / (1.0f + t));
-      const double n = (double)G.N;
-      // the folded prior site (mi_prior): log p(a_k) and d/da_k of the per-particle parameter a_k
-      float prior_lp = 0.0f, prior_d = 0.0f;
-      if (G.prior.present != 0) {
-        const float a = role_scalar(G, st, 0, k);
-        Elem pe;
-        if (G.prior.family == MI_BETA) eval_beta(G.prior.constant[0], G.prior.constant[1], a, pe);
-        else if (G.prior.family == MI_NORMAL) eval_normal(G.prior.constant[0], G.prior.constant[1], a, pe);
-        else eval_gamma(G.prior.constant[0], G.prior.constant[1], a, pe);
-        prior_lp = pe.lp;
-        prior_d = pe.d[2];
-        fl_prior |= (pe.param_bad ? MI_FLAG_PARAM : 0u) | (pe.support_bad ? MI_FLAG_SUPPORT : 0u);
-      }
-      const float cv = (float)(-n * softplus) + prior_lp;
-      if (ksummed) csum += (double)cv;
-      else part[extra * K + k] = cv;
-      if (slot_a >= 0) {
-        const float e = w * (float)(-n * sig * (double)dlp) + w * prior_d;
-        if (rank1) {
-          slot_part[nseg + k] = w * dlp;         // f[k]
-          slot_part[nseg + K + k] = e;           // e[k]
-        } else {
-          slot_part[extra * K + k] = e;
+      if (k < K) {
+        float l, dlp;
+        (void)logits(p, l, dlp);
+        const float t = expf(-fabsf(l));
+        const double softplus = (double)(fmaxf(l, 0.0f) + log1pf(t));
+        const double sig = (double)(l >= 0.0f ? 1.0f / (1.0f + t) : t / (1.0f + t));
+        const double n = (double)G.N;
+        // the folded prior site (mi_prior): log p(a_k) and d/da_k of the per-particle parameter a_k
+        float prior_lp = 0.0f, prior_d = 0.0f;
+        if (G.prior.present != 0) {
+          const float a = role_scalar(G, st, 0, k);
+          Elem pe;
+          if (G.prior.family == MI_BETA) eval_beta(G.prior.constant[0], G.prior.constant[1], a, pe);
+          else if (G.prior.family == MI_NORMAL) eval_normal(G.prior.constant[0], G.prior.constant[1], a, pe);
+          else eval_gamma(G.prior.constant[0], G.prior.constant[1], a, pe);
+          prior_lp = pe.lp;
+          prior_d = pe.d[2];
+          fl_prior |= (pe.param_bad ? MI_FLAG_PARAM : 0u) | (pe.support_bad ? MI_FLAG_SUPPORT : 0u);
+        }
+        const float cv = (float)(-n * softplus) + prior_lp;
+        if (ksummed) csum += (double)cv;
+        else part[extra * K + k] = cv;
+        if (slot_a >= 0) {
+          const float e = w * (float)(-n * sig * (double)dlp) + w * prior_d;
+          if (rank1) {
+            slot_part[nseg + k] = w * dlp;         // f[k]
+            slot_part[nseg + K + k] = e;           // e[k]
+          } else {
+            slot_part[extra * K + k] = e;
+          }
         }
       }
+      if (ksummed && spread) {   // (uniform over the workgroup, as the loop's bounds)
+        csum = block_sum(csum, dscratch);
+        if (threadIdx.x == 0) ksum[(chunks + p) * gy + kblock] = csum;
+        csum = 0.0;
+      }
     }
-    if (ksummed) {   // (the branch is uniform over the workgroup)
+    if (ksummed && !spread) {
       csum = block_sum(csum, dscratch);
-      if (threadIdx.x == 0) ksum[(chunks + (spread ? c : 0)) * gy + kblock] = csum;
+      if (threadIdx.x == 0) ksum[chunks * gy + kblock] = csum;
     }
   }
-  if (rank1 && slot_a >= 0 && kblock == 0 && threadIdx.x == 0 && c == 0) slot_part[extra] = 0.0f;
+  if (rank1 && slot_a >= 0 && kblock == 0 && threadIdx.x == 0 && g == 0) slot_part[extra] = 0.0f;
   publish_flags(flags, fl);
   if (G.prior.present != 0) publish_flags(G.prior.flags, fl_prior);
   span_end(G.stamps, t0);
+  MI_TL_END(0, g, kblock);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1409,8 +1613,7 @@ Plan make_plan(const mi_group* g) {
     if (smem) p.chunk = smem_chunk(g->N, ceil_div(g->K, mi::kBcastThreads * kSmemP));
     const int64_t chunks = ceil_div(g->N, smem ? p.chunk : mi::kBcastChunk);
     p.nseg = smem ? chunks + 1 : chunks;   // k_site_bcast_smem: + the particle-constant segment
-    const int64_t side = (smem && g->side.out != nullptr)
-                             ? ceil_div(2 * g->side.K * g->side.N, mi::kBcastThreads) : 0;
+    const int64_t side = smem ? mi::beta_side_blocks(g->side) : 0;
     p.grid = dim3((unsigned)(chunks + side),
                   (unsigned)ceil_div(g->K, mi::kBcastThreads * (smem ? kSmemP : mi::kBcastP)));
     return p;
@@ -1526,6 +1729,46 @@ bool smem_rank1(const mi_group* g, const Plan& p) {
   return g->num_slots == 1 && g->compute_grads && p.nseg >= 3 && p.nseg <= MI_REDUCE_MAX_SEG;
 }
 
+// The workgroups of the matrix instantiation with CPW chunks each that the current device holds at
+// once: compute units x the runtime's occupancy answer for that instantiation (registers and LDS),
+// asked once per instantiation and device. 0: the runtime gave no answer.
+template <int FAM, int CPW>
+int64_t smem_matrix_slots() {
+  constexpr int kDevices = 16;
+  static std::atomic<int64_t> cache[kDevices];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  const bool keep = dev >= 0 && dev < kDevices;
+  if (keep) {
+    const int64_t v = cache[dev].load(std::memory_order_relaxed);
+    if (v != 0) return v;
+  }
+  int per_cu = 0, cus = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
+          &per_cu, mi::k_site_bcast_smem<FAM, kSmemP, false, true, CPW>, mi::kBcastThreads, 0) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    return 0;
+  const int64_t v = (int64_t)per_cu * (int64_t)cus;
+  if (keep) cache[dev].store(v, std::memory_order_relaxed);
+  return v;
+}
+
+// Chunks per workgroup of a matrix launch: the smallest of {1, 2, 4} whose grid, chunk groups x
+// particle blocks, fits one round of resident workgroups, else 4. A grid that fits as it is keeps
+// 1: the launch it always was. C2 (255 chunks x 4 particle blocks, two workgroups on each of 256
+// CUs): 2, 128 groups x 4 = 512 workgroups. MININF_AMD_BCAST_CPW = 1, 2 or 4 forces it (0, unset:
+// this choice).
+template <int FAM>
+int smem_cpw(int64_t chunks, int64_t gy) {
+  const int forced = env_int("MININF_AMD_BCAST_CPW", 0);
+  if (forced == 1 || forced == 2 || forced == 4) return forced;
+  const int64_t one = smem_matrix_slots<FAM, 1>();
+  if (one <= 0 || chunks * gy <= one) return 1;
+  const int64_t two = smem_matrix_slots<FAM, 2>();
+  if (two <= 0) return 1;
+  return ceil_div(chunks, 2) * gy <= two ? 2 : 4;
+}
+
 template <int FAM>
 void launch_smem(const mi_group& G, const Plan& p, float* part, uint32_t* flags, hipStream_t s,
                  double* ksum) {
@@ -1552,10 +1795,26 @@ void launch_smem(const mi_group& G, const Plan& p, float* part, uint32_t* flags,
   // K 64 n 1e6 17.0 / 33.4, K 256 n 1e6 17.5 / 33.9, K 64 n 1024 13.9 / 16.8, K 4096 n 4096
   // 22.0 / 35.0, K 1024 n 65536 19.8 / 32.8; uniform random x, every chunk falling back to the
   // scalar-load loop at two waves per SIMD, 98.7 / 96.7).
-  else if (env_int("MININF_AMD_BCAST_MFMA", 1) != 0)
-    hipLaunchKernelGGL((mi::k_site_bcast_smem<FAM, kSmemP, false, true>), grid, block, 0, s, G,
-                       part, p.nseg, gy, rank1, p.chunk, flags, ksum);
-  else
+  // (Those figures are the one-chunk launch's. Re-measured with several chunks per workgroup in
+  // the tree, parent / this kernel: K 4096 n 1e6 36.6 / 33.5 at two chunks per workgroup, one
+  // element off alignment 41.4 / 38.9, uniform random x 99.6 / 92.5; the shapes that keep one chunk
+  // 0.3-0.5 us slower, K 64 n 1e6 16.9 / 17.2, K 256 n 1e6 17.5 / 17.8, K 64 n 1024 14.0 / 14.4,
+  // K 4096 n 4096 22.1 / 22.5, K 1024 n 65536 19.7 / 20.2: DESIGN.md section 0q.)
+  // Chunks per workgroup (above): 1 launches the grid above; 2 and 4 launch one workgroup per
+  // (chunk group, particle block) behind the side job's workgroups, those padded to a multiple of 8.
+  else if (env_int("MININF_AMD_BCAST_MFMA", 1) != 0) {
+    const int cpw = smem_cpw<FAM>(chunks, gy);
+    const dim3 grouped((unsigned)(ceil_div(ceil_div(chunks, cpw), 8) * 8 * gy + ceil_div(side, 8) * 8));
+    if (cpw == 4)
+      hipLaunchKernelGGL((mi::k_site_bcast_smem<FAM, kSmemP, false, true, 4>), grouped, block, 0, s,
+                         G, part, p.nseg, gy, rank1, p.chunk, flags, ksum);
+    else if (cpw == 2)
+      hipLaunchKernelGGL((mi::k_site_bcast_smem<FAM, kSmemP, false, true, 2>), grouped, block, 0, s,
+                         G, part, p.nseg, gy, rank1, p.chunk, flags, ksum);
+    else
+      hipLaunchKernelGGL((mi::k_site_bcast_smem<FAM, kSmemP, false, true>), grid, block, 0, s, G,
+                         part, p.nseg, gy, rank1, p.chunk, flags, ksum);
+  } else
     hipLaunchKernelGGL((mi::k_site_bcast_smem<FAM, kSmemP>), grid, block, 0, s, G,
                        part, p.nseg, gy, rank1, p.chunk, flags, ksum);
 }
@@ -1962,3 +2221,16 @@ int mi_categorical_forward(const float* logits, int64_t stride_k, int64_t stride
 }
 
 }  // extern "C"
+
+#ifdef MI_SITES_TIMELINE
+// The timeline build's accessors (tools/c2_timeline.py): copy the rows out, clear them.
+extern "C" int mi_debug_timeline(void* out, size_t bytes) {
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(mi::g_tl), bytes, 0, hipMemcpyDeviceToHost);
+}
+extern "C" int mi_debug_timeline_clear() {
+  void* rows = nullptr;
+  hipError_t e = hipGetSymbolAddress(&rows, HIP_SYMBOL(mi::g_tl));
+  if (e == hipSuccess) e = hipMemset(rows, 0, sizeof(unsigned long long) * mi::kTimelineRows * 8);
+  return (int)e;
+}
+#endif

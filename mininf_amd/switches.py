@@ -44,6 +44,8 @@ ELSEWHERE = {
                       "measurement of the broadcast site kernel (default 0)",
     "BCAST_MFMA": "read in C++, not through this module: 0 keeps chunks of 0/1 data off the bf16 "
                   "matrix cores in the broadcast site kernel (default on; BCAST_SUFFSTAT wins)",
+    "BCAST_CPW": "read in C++, not through this module: 1, 2 or 4 chunks per workgroup of the "
+                 "broadcast site kernel's matrix launch (unset or 0: the smallest that fits one round)",
     "ELBO_EXTERNAL": "read in C++, not through this module: take the large ELBO launch's path at "
                      "any size (tests; default 0)",
     "ELBO_KRED": "named in a comment of csrc/elbo.hip only: no code reads it any more",

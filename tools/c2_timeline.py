@@ -1,13 +1,17 @@
 """
-Where C2's site kernel (k_site_bcast_smem) spends its time, per workgroup: a variant build of
-sites.hip that stamps thread 0's wall clock (s_memrealtime, 100 MHz) at entry, after the
-per-particle logits, after the FMA loops, after the chunk sum and at exit into a device array.
+Where C2's site kernel (k_site_bcast_smem, the matrix instantiation) spends its time, per workgroup:
+a build of sites.hip with MI_SITES_TIMELINE defined, in which thread 0 of every workgroup stamps
+the constant-rate clock (s_memrealtime, 100 MHz) at entry, after the per-particle logits, after the
+chunk pass and its barrier round, after the first matrix pass, after the matrix loop, after the
+chunks' values are stored and at exit (the MI_TL points of sites.hip).
 `run` replays the C2 bench step (24 steps per graph replay, as bench.py), then one more replay with
-the array cleared, and prints the phase statistics of the last launch of that replay -- by dispatch
-rank (block b is the b / 256-th workgroup of its CU in a one-round grid) and by XCD.
+the rows cleared, and prints the phase statistics of the last launch of that replay -- by dispatch
+rank on the CU (block b is the b / 256-th workgroup of its CU), for the particle-constant
+workgroups (chunk groups 0-3) and for the side job -- and which workgroups leave last.
+MININF_AMD_BCAST_CPW selects the chunks per workgroup as in any build.
 
     python tools/c2_timeline.py build [name]   (on the CPU: tools/_variants/<name, c2tl>/)
-    MININF_AMD_LIB=tools/_variants/c2tl/libmininf_amd.so python tools/c2_timeline.py run [rows.npy]
+    MININF_AMD_LIB=tools/_variants/c2tl/libmininf_amd.so python tools/c2_timeline.py run [out.json]
 """
 import ctypes
 import json
@@ -27,72 +31,13 @@ from mininf_amd.graph import StepGraph  # noqa: E402
 
 
 def build_variant(name="c2tl"):
-    """The timeline variant of the tree's sites.hip, through tools/variant_build.py."""
+    """The timeline build of the tree's sites.hip, through tools/variant_build.py."""
     import subprocess
     import tempfile
     src = open(os.path.join(ROOT, "mininf_amd", "csrc", "sites.hip")).read()
-
-    def rep(old, new):
-        nonlocal src
-        assert src.count(old) == 1, old[:60]
-        src = src.replace(old, new)
-    rep("constexpr int kSmemMaxChunk", "__device__ unsigned long long g_tl[8192 * 8];\nconstexpr int kSmemMaxChunk")
-    rep("""  const int64_t b = blockIdx.x;
-  if (b >= padded * gy) {   // workgroups past the chunks: the side job (mi_side)
-    const unsigned long long ts = span_begin(G.stamps);   // (the launch's span includes them)
-    beta_side_block(G.side, b - padded * gy);
-    span_end(G.stamps, ts);
-    return;
-  }""", """  const int64_t b = blockIdx.x;
-  const unsigned long long T0 = __builtin_amdgcn_s_memrealtime();
-  if (b >= padded * gy) {   // workgroups past the chunks: the side job (mi_side)
-    const unsigned long long ts = span_begin(G.stamps);
-    beta_side_block(G.side, b - padded * gy);
-    span_end(G.stamps, ts);
-    __syncthreads();
-    if (threadIdx.x == 0) { g_tl[b * 8] = T0; g_tl[b * 8 + 4] = __builtin_amdgcn_s_memrealtime(); g_tl[b * 8 + 5] = 1; }
-    return;
-  }""")
-    rep("""  double acc[kSmemP];
-#pragma unroll
-  for (int p = 0; p < kSmemP; ++p) acc[p] = 0.0;""", """  if (threadIdx.x == 0) { float z = 0.f;
-#pragma unroll
-    for (int p = 0; p < kSmemP; ++p) z += ld[p].x;
-    __asm__ volatile("" :: "v"(z)); }
-  const unsigned long long T1 = __builtin_amdgcn_s_memrealtime();
-  double acc[kSmemP];
-#pragma unroll
-  for (int p = 0; p < kSmemP; ++p) acc[p] = 0.0;""")
-    rep("""  // ---- chunk sum and support flags (vector loads, L2-resident by now)""",
-        """  const unsigned long long T2 = __builtin_amdgcn_s_memrealtime();
-  // ---- chunk sum and support flags (vector loads, L2-resident by now)""")
-    rep("""  s_a = block_sum(s_a, scratch);
-  if (SUFF) {""", """  s_a = block_sum(s_a, scratch);
-  const unsigned long long T3 = __builtin_amdgcn_s_memrealtime();
-  if (SUFF) {""")
-    rep("""  if (G.prior.present != 0) publish_flags(G.prior.flags, fl_prior);
-  span_end(G.stamps, t0);
-}""", """  if (G.prior.present != 0) publish_flags(G.prior.flags, fl_prior);
-  span_end(G.stamps, t0);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    g_tl[b * 8] = T0; g_tl[b * 8 + 1] = T1; g_tl[b * 8 + 2] = T2; g_tl[b * 8 + 3] = T3;
-    g_tl[b * 8 + 4] = __builtin_amdgcn_s_memrealtime(); g_tl[b * 8 + 5] = 0; g_tl[b * 8 + 6] = c;
-    g_tl[b * 8 + 7] = kblock;
-  }
-}""")
-    src += """
-extern "C" int mi_debug_timeline(void* out, size_t bytes) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(mi::g_tl), bytes, 0, hipMemcpyDeviceToHost);
-}
-extern "C" int mi_debug_timeline_clear() {
-  static unsigned long long zeros[8192 * 8];
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(mi::g_tl), zeros, sizeof(zeros), 0, hipMemcpyHostToDevice);
-}
-"""
     with tempfile.TemporaryDirectory() as tmp:
         path = os.path.join(tmp, "sites.hip")
-        open(path, "w").write(src)
+        open(path, "w").write("#define MI_SITES_TIMELINE 1\n" + src)
         subprocess.run([sys.executable, os.path.join(ROOT, "tools", "variant_build.py"), name,
                         f"sites.hip={path}"], check=True)
 
@@ -100,7 +45,6 @@ extern "C" int mi_debug_timeline_clear() {
 def main():
     dev = torch.device("cuda:0")
     n, K = 1_000_000, 4096
-    gy = K // 1024
     x = (torch.rand(n, generator=torch.Generator().manual_seed(0)) < 0.7).float().to(dev)
 
     def model():
@@ -131,50 +75,47 @@ def main():
     raw = np.zeros(8192 * 8, dtype=np.uint64)
     assert lib.mi_debug_timeline(raw.ctypes.data, raw.nbytes) == 0
     rows = raw.reshape(-1, 8).astype(np.int64)
-    rows = rows[rows[:, 0] > 0]
-    main_rows = rows[rows[:, 5] == 0]
-    side = rows[rows[:, 5] == 1]
+    block = np.nonzero(rows[:, 0] > 0)[0]           # blockIdx.x of every workgroup that ran
+    rows = rows[block]
+    kind, kblock, group = rows[:, 7] % 2, (rows[:, 7] // 2) % 16, rows[:, 7] // 32
     base = rows[:, 0].min()
-    us = lambda v: (v - base) / 100.0   # noqa: E731
-    t = [us(main_rows[:, i]) for i in range(5)]
-    out = {"workgroups": int(main_rows.shape[0]), "side_workgroups": int(side.shape[0]),
-           "kernel_span_us": float((rows[:, 4].max() - base) / 100.0)}
+    t = (rows[:, :7] - base) / 100.0                # us since the first workgroup's entry
+    main_wg, side = kind == 0, kind == 1
 
     def stats(v):
-        return [round(float(np.min(v)), 2), round(float(np.percentile(v, 10)), 2),
-                round(float(np.median(v)), 2), round(float(np.percentile(v, 90)), 2),
-                round(float(np.max(v)), 2)]
-    out["min/p10/median/p90/max (us)"] = {
-        "entry": stats(t[0]), "logits (prologue)": stats(t[1] - t[0]),
-        "fma loops": stats(t[2] - t[1]), "chunk sum + block sum": stats(t[3] - t[2]),
-        "partials + flags (epilogue)": stats(t[4] - t[3]), "exit": stats(t[4]),
-    }
-    if side.shape[0]:
-        out["side job (entry, exit)"] = {"entry": stats(us(side[:, 0])), "exit": stats(us(side[:, 4]))}
-    c0 = main_rows[main_rows[:, 6] == 0]
-    if c0.shape[0]:
-        out["chunk-0 workgroups epilogue (us)"] = [round(float(v), 2) for v in (c0[:, 4] - c0[:, 3]) / 100.0]
-    late = np.argsort(-t[4])[:8]
-    out["last 8 to exit: (chunk, kblock, entry, loop, exit)"] = [
-        (int(main_rows[i, 6]), int(main_rows[i, 7]), round(float(t[0][i]), 2),
-         round(float(t[2][i] - t[1][i]), 2), round(float(t[4][i]), 2)) for i in late]
-    xcd = main_rows[:, 6] % 8
-    out["per XCD (c % 8): median prologue, loop, epilogue, exit; max exit"] = {
-        int(q): [round(float(np.median((t[1] - t[0])[xcd == q])), 2),
-                 round(float(np.median((t[2] - t[1])[xcd == q])), 2),
-                 round(float(np.median((t[4] - t[3])[xcd == q])), 2),
-                 round(float(np.median(t[4][xcd == q])), 2), round(float(np.max(t[4][xcd == q])), 2)]
-        for q in range(8)}
-    c, kb = main_rows[:, 6], main_rows[:, 7]
-    b = (c // 8) * (8 * gy) + kb * 8 + c % 8
-    out["by dispatch rank (b // 256): n, median prologue, loop, exit; min, max exit"] = {
-        int(q): [int(((b // 256) == q).sum())] + [round(float(np.median(v[(b // 256) == q])), 2)
-                                                   for v in (t[1] - t[0], t[2] - t[1], t[4])] +
-        [round(float(t[4][(b // 256) == q].min()), 2), round(float(t[4][(b // 256) == q].max()), 2)]
-        for q in range(int(b.max()) // 256 + 1)}
+        if v.size == 0:
+            return None
+        return [round(float(q), 2) for q in (np.min(v), np.percentile(v, 10), np.median(v),
+                                              np.percentile(v, 90), np.max(v))]
+
+    def phases(sel):
+        m = t[sel]
+        return {"n": int(sel.sum()), "entry": stats(m[:, 0]), "logits": stats(m[:, 1] - m[:, 0]),
+                "chunk pass + barrier": stats(m[:, 2] - m[:, 1]),
+                "first matrix pass": stats(m[:, 3] - m[:, 2]),
+                "later matrix passes": stats(m[:, 4] - m[:, 3]),
+                "value sums + stores": stats(m[:, 5] - m[:, 4]),
+                "slot rows, constant segment, flags": stats(m[:, 6] - m[:, 5]),
+                "exit": stats(m[:, 6])}
+    out = {"cpw": os.environ.get("MININF_AMD_BCAST_CPW", "auto"),
+           "workgroups": int(main_wg.sum()), "side_workgroups": int(side.sum()),
+           "kernel_span_us": round(float(t[:, 6].max()), 2),
+           "columns": "min / p10 / median / p90 / max (us)",
+           "all main workgroups": phases(main_wg),
+           "by dispatch rank (blockIdx.x // 256)": {
+               int(q): phases(main_wg & (block // 256 == q)) for q in np.unique(block[main_wg] // 256)},
+           "particle-constant workgroups (chunk groups 0-3)": phases(main_wg & (group < 4)),
+           "other main workgroups": phases(main_wg & (group >= 4))}
+    if side.any():
+        out["side job"] = {"n": int(side.sum()), "entry": stats(t[side, 0]), "exit": stats(t[side, 6])}
+    last = np.argsort(-t[:, 6])[:8]
+    out["last 8 to exit: (blockIdx.x, side job, chunk group, particle block, entry, exit)"] = [
+        (int(block[i]), int(kind[i]), int(group[i]), int(kblock[i]), round(float(t[i, 0]), 2),
+         round(float(t[i, 6]), 2)) for i in last]
+    text = json.dumps(out, indent=1)
     if len(sys.argv) > 2:
-        np.save(sys.argv[2], rows - np.array([base, base, base, base, base, 0, 0, 0]))
-    print(json.dumps(out, indent=1))
+        open(sys.argv[2], "w").write(text + "\n")
+    print(text)
 
 
 if __name__ == "__main__":
