@@ -671,56 +671,67 @@ __device__ unsigned long long g_tl[kTimelineRows * 8];
 #endif
 
 // The matrix loop of k_site_bcast_smem (mode bit 3, MININF_AMD_BCAST_MFMA): a chunk whose elements
-// are all exactly 0 or 1 is summed on the bf16 matrix cores with no rounding anywhere.
-//   * x_i in {0, 1} is exact in bf16.
-//   * a finite fp32 logit is the exact sum of three bf16 pieces, h = bf16(l), m = bf16(l - h),
-//     lo = bf16(l - h - m) (the differences are exact in fp32; pieces below bf16's normal range
-//     lose at most 2^-126 each, and a non-finite logit is carried as (l, 0, 0)).
-//   * every accumulator element is (a count <= 4096) x (one piece): 13 + 8 bits, exact in fp32 in
-//     any order as long as each piece keeps accumulators of its own. The pieces meet in fp64.
-// D = A B with v_mfma_f32_16x16x32_bf16: A[row][k] holds 512 consecutive elements of the staged
-// chunk (any element may sit in any slot: all of D's rows are added up at the end), B[k][col] is
-// the piece of the tile's particle `col` in every k. A wave takes the 4 x 64 particles its lanes
-// own in passes of kMatrixP particles per lane: 4 column tiles x 3 pieces per particle slot, each
-// with a 4-register accumulator and a 4-register B fragment -- 2 x 4 x 3 x (4 + 4) = 192 registers
-// a pass, two waves per SIMD (all four slots in one pass take 384: one wave per SIMD).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));   // a fragment as its four registers
+// are all exactly 0 or 1 is summed on the int8 matrix cores with no rounding anywhere.
+//   * x_i in {0, 1} is exact in int8.
+//   * a finite fp32 logit with sign s, biased exponent e and fraction f is (-1)^s M 2^E exactly,
+//     M = f + (e > 0 ? 2^23 : 0) its significand and E = max(e, 1) - 150 (subnormals and zeros
+//     included: nothing is lost below any format's normal range). With c = (e > 0 ? 2^23 : 0) + 2^22
+//     the rest r = M - c = f - 2^22 lies in [-2^22, 2^22) and is three balanced base-256 digits,
+//     r = d0 + 256 d1 + 65536 d2, each in [-128, 127]: three int8 pieces.
+//   * every accumulator element is (a count <= 4096) x (one digit), |.| <= 2^19, exact in int32 in
+//     any order; each digit keeps accumulators of its own. With n1 the chunk's count of ones,
+//     S = c n1 + D0 + 256 D1 + 65536 D2 = M n1 (< 2^36, int64) and the chunk's total is
+//     (-1)^s S 2^E in fp64, a power-of-two scale: l_k sum_i x_i exactly.
+// Every eval is still its own multiply-accumulate, x_i times a digit of l_k, but on the 23 fraction
+// bits recentred by 2^22 only: the implicit leading one and the recentring constant, c, are the same
+// for every element and enter once per (chunk, particle) through the count of ones, which the
+// kernel has as the chunk sum it forms for the gradient.
+// D = A B with v_mfma_i32_16x16x64_i8: A[row][k] holds 1024 consecutive elements of the staged
+// chunk (any element may sit in any slot: B is constant over k and all of D's rows are added up at
+// the end, so only the C/D lane map is used), B[k][col] is the digit of the tile's particle `col`
+// in every k. A wave takes the 4 x 64 particles its lanes own in passes of kMatrixP particles per
+// lane: 4 column tiles x 3 digits per particle slot, each with a 4-register accumulator and a
+// 4-register B fragment. One chunk per workgroup: kMatrixP = 2 slots a pass, 2 x 4 x 3 x (4 + 4) =
+// 192 registers and 24 instructions per fragment, two waves per SIMD (all four slots in one pass
+// take 384: one wave per SIMD). Several chunks per workgroup: one slot a pass, 96 registers and 12
+// instructions per fragment, three waves per SIMD (the digits stay live across a chunk's read-out).
+typedef int i32x4 __attribute__((ext_vector_type(4)));   // a fragment, or an accumulator, as its four registers
 constexpr int kMatrixP = 2;
-constexpr int kFragElems = 512;   // elements per A fragment: 16 rows x 32 k
+constexpr int kFragElems = 1024;   // elements per A fragment: 16 rows x 64 k
 
-MI_DEV float bf16_round(float v) { return (float)(__bf16)v; }
-
-// The three pieces of a logit, as the bf16 pattern repeated over a B fragment's eight k.
+// The three digits of a logit's recentred fraction, each as its byte repeated over a B fragment's
+// sixteen k. (A non-finite logit gets digits too; its total is made on the vector side.)
 MI_DEV void logit_pieces(float l, i32x4 (&b)[3]) {
-  float piece[3] = {l, 0.0f, 0.0f};
-  if (__builtin_isfinite(l)) {
-    float h = bf16_round(l);
-    // (rounding to nearest can reach infinity just below FLT_MAX: truncate there instead)
-    if (!__builtin_isfinite(h)) h = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, l) & 0xffff0000u);
-    const float r = l - h;
-    const float m = bf16_round(r);
-    piece[0] = h;
-    piece[1] = m;
-    piece[2] = bf16_round(r - m);
-  }
+  int r = (int)(__builtin_bit_cast(uint32_t, l) & 0x7fffffu) - (1 << 22);
 #pragma unroll
   for (int q = 0; q < 3; ++q) {
-    const int v = (int)(__builtin_bit_cast(uint32_t, piece[q]) >> 16);   // (a bf16 value: exact)
-    const int vv = v | (v << 16);
+    const int d = ((r & 0xff) ^ 0x80) - 0x80;   // the balanced digit: r's low byte, signed
+    r = (r - d) >> 8;                           // (exact: r - d is a multiple of 256)
+    const int vv = (d & 0xff) * 0x01010101;
     b[q] = i32x4{vv, vv, vv, vv};
   }
 }
 
+// l n1 from the digit sums D of one (chunk, particle): (-1)^s (c n1 + D0 + 256 D1 + 65536 D2) 2^E,
+// exact in fp64 (a zero total is +0, as a sum from 0.0 is). A non-finite logit: l n1, non-finite.
+MI_DEV double logit_total(float l, int n1, const int (&D)[3]) {
+  const uint32_t u = __builtin_bit_cast(uint32_t, l);
+  const int e = (int)((u >> 23) & 0xffu);
+  if (e == 0xff) return (double)l * (double)n1;   // (an infinity over no ones: NaN)
+  const int64_t c = (e > 0 ? (int64_t)1 << 23 : 0) + ((int64_t)1 << 22);
+  const int64_t S = c * n1 + D[0] + 256 * (int64_t)D[1] + 65536 * (int64_t)D[2];
+  const double scale = __builtin_bit_cast(double, (uint64_t)(max(e, 1) - 150 + 1023) << 52);
+  return (double)((u >> 31) != 0u ? -S : S) * scale;
+}
+
 // sum_i x_i l_k for the kSmemP particles of every lane, for each of the workgroup's chunks whose bit
-// is set in `mat`: chunk j staged at xa + j kSmemMaxChunk as bf16 (zeros past its end, up to a whole
-// fragment), nfrag(j) >= 1 fragments long. The pieces of a pass are split once and every chunk walks
-// them; a chunk's accumulators are read out before the next chunk starts (each chunk keeps a partial
-// of its own), and `fold(j, p, total)` takes the total of chunk j and particle slot p: slots in
-// order within a chunk. `first_k`: the wave's first particle of slot 0.
-template <int kSmemP, int CPW, int MP, typename Frags, typename Fold>
-MI_DEV void bcast_matrix_loop(const __bf16* xa, uint32_t mat, Frags nfrag,
+// is set in `mat`: chunk j staged at xa + j kSmemMaxChunk as int8 (zeros past its end, up to a whole
+// fragment), nfrag(j) >= 1 fragments long, ones(j) of its elements a one. The digits of a pass are
+// split once and every chunk walks them; a chunk's accumulators are read out before the next chunk
+// starts (each chunk keeps a partial of its own), and `fold(j, p, total)` takes the total of chunk j
+// and particle slot p: slots in order within a chunk. `first_k`: the wave's first particle of slot 0.
+template <int kSmemP, int CPW, int MP, typename Frags, typename Ones, typename Fold>
+MI_DEV void bcast_matrix_loop(const signed char* xa, uint32_t mat, Frags nfrag, Ones ones,
                               const f32x2 (&ld)[kSmemP], int64_t first_k, int64_t K, Fold fold) {
   static_assert(kSmemP % MP == 0, "whole passes");
   const int lane = threadIdx.x & 63;
@@ -740,36 +751,38 @@ MI_DEV void bcast_matrix_loop(const __bf16* xa, uint32_t mat, Frags nfrag,
       if (((mat >> j) & 1u) == 0u) continue;   // (uniform over the workgroup)
       const i32x4* frag = reinterpret_cast<const i32x4*>(xa + j * kSmemMaxChunk) + lane;
       const int nf = nfrag(j);
-      f32x4 d[MP][4][3];
+      const int n1 = ones(j);
+      i32x4 d[MP][4][3];
 #pragma unroll
       for (int pp = 0; pp < MP; ++pp)
 #pragma unroll
         for (int g = 0; g < 4; ++g)
 #pragma unroll
-          for (int q = 0; q < 3; ++q) d[pp][g][q] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+          for (int q = 0; q < 3; ++q) d[pp][g][q] = i32x4{0, 0, 0, 0};
       // The loop is written out: from the builtin the compiler routes half the accumulators through
       // a scratch tile, four register moves and a wait per instruction. Accumulators are tied in
-      // AGPRs, fragments stay in VGPRs; between two instructions on one accumulator stand 23 others.
+      // AGPRs, fragments stay in VGPRs; between two instructions on one accumulator stand 23 others
+      // (11 with one slot a pass).
       // The compiler's hazard recogniser does not see inside the assembly: after a toolchain change
       // read the ISA of this loop again (the accumulators' zeroing before the first instruction,
       // the s_waitcnt before the fragment's first use, the waits after the loop).
       int f = 0;
       i32x4 next = frag[0];
       do {   // (nf >= 1: a chunk is never empty. The next fragment's read is issued ahead of
-             // this fragment's 24 instructions and waited for behind them: one iteration of overlap,
+             // this fragment's 24 (or 12) instructions and waited for behind them: one iteration of overlap,
              // not a second buffer.)
         const i32x4 a = next;
-        next = frag[min(f + 1, nf - 1) * (kFragElems / 8)];
+        next = frag[min(f + 1, nf - 1) * (kFragElems / 16)];
 #pragma unroll
         for (int pp = 0; pp < MP; ++pp)
 #pragma unroll
           for (int g = 0; g < 4; ++g)
 #pragma unroll
             for (int q = 0; q < 3; ++q)
-              __asm__ volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0"
+              __asm__ volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %0"
                                : "+a"(d[pp][g][q]) : "v"(a), "v"(b[pp][g][q]));
       } while (++f < nf);
-      // v_mfma_f32_16x16x32_bf16 is an 8-pass instruction, and a VALU read of a matrix result
+      // v_mfma_i32_16x16x64_i8 is an 8-pass instruction, and a VALU read of a matrix result
       // has to stand passes + 3 = 11 wait states behind it (19 behind a 16-pass one; the compiler's
       // hazard table for gfx950). Each statement below waits 32 (two s_nop 15); there are MP
       // of them, in order, each tied to half the accumulators. They stand before every read-out:
@@ -782,40 +795,39 @@ MI_DEV void bcast_matrix_loop(const __bf16* xa, uint32_t mat, Frags nfrag,
                            "+a"(d[pp][2][2]), "+a"(d[pp][3][0]), "+a"(d[pp][3][1]), "+a"(d[pp][3][2]));
       // D's rows: four registers, then the four lane groups. Lane group g keeps tile g (its lanes
       // own that tile's particles), so the groups trade halves instead of all summing every tile.
-      // (fp32, exact: count x piece.)
+      // (int32, exact: count x digit.) The lane then owns the digit sums of its own particle.
 #pragma unroll
       for (int pp = 0; pp < MP; ++pp) {
-        double total = 0.0;
+        int D[3];
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-          float v[4];
+          int v[4];
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
             v[g] = (d[pp][g][q].x + d[pp][g][q].y) + (d[pp][g][q].z + d[pp][g][q].w);
           }
           const bool hi = grp >= 2, odd = (grp & 1) != 0;
-          const float w0 = (hi ? v[2] : v[0]) + __shfl_xor(hi ? v[0] : v[2], 32, 64);
-          const float w1 = (hi ? v[3] : v[1]) + __shfl_xor(hi ? v[1] : v[3], 32, 64);
-          const float t = (odd ? w1 : w0) + __shfl_xor(odd ? w0 : w1, 16, 64);
-          total += (double)t;
+          const int w0 = (hi ? v[2] : v[0]) + __shfl_xor(hi ? v[0] : v[2], 32, 64);
+          const int w1 = (hi ? v[3] : v[1]) + __shfl_xor(hi ? v[1] : v[3], 32, 64);
+          D[q] = (odd ? w1 : w0) + __shfl_xor(odd ? w0 : w1, 16, 64);
         }
-        fold(j, p0 + pp, total);
+        fold(j, p0 + pp, logit_total(ld[p0 + pp].x, n1, D));
       }
     }
   }
 }
 
-// MATRIX: the instantiation that holds the matrix loop (240 / 236 registers with 96 AGPRs and 8 KB
+// MATRIX: the instantiation that holds the matrix loop (236 / 232 registers with 96 AGPRs and 4 KB
 // of LDS: two waves per SIMD). Without it the kernel is the scalar-load loop alone, at its 90
 // registers and four workgroups per CU: what MININF_AMD_BCAST_MFMA=0 launches.
-// (CPW = 2 / 4: one particle slot per matrix pass, 152 / 160 registers with 48 AGPRs, 20 / 40 KB
+// (CPW = 2 / 4: one particle slot per matrix pass, 152 / 148 registers with 48 AGPRs, 12 / 24 KB
 // of LDS, no scratch: three waves per SIMD.)
 // CPW (chunks per workgroup, the matrix instantiation only; MININF_AMD_BCAST_CPW): the workgroup
 // owns particle block `kblock` and the CPW consecutive chunks of chunk group g, [g CPW, min((g + 1)
 // CPW, chunks)). The chunk plan, every partial and every index written are those of CPW = 1; what
 // is paid once per workgroup instead of once per chunk is the setup (arguments, parameters, logits),
 // the latency of the chunk pass (all the group's loads are in flight together), one barrier round
-// for all the chunk sums and flags, the piece splits of a pass and the slot epilogue. launch_smem
+// for all the chunk sums and flags, the digit splits of a pass and the slot epilogue. launch_smem
 // picks CPW so that the grid fits one round of resident workgroups. With CPW > 1 the side job's
 // workgroups (padded to a multiple of 8: the XCD mapping stays) come first in the grid.
 template <int FAMILY, int kSmemP, bool SUFF = false, bool MATRIX = false, int CPW = 1>
@@ -826,13 +838,13 @@ __global__ __launch_bounds__(kBcastThreads) void k_site_bcast_smem(const mi_grou
                                                                    uint32_t* __restrict__ flags,
                                                                    double* __restrict__ ksum) {
   static_assert(CPW == 1 || (MATRIX && !SUFF), "several chunks per workgroup: the matrix loop only");
-  static_assert(CPW >= 1 && CPW <= 4, "the staged chunks: at most 32 KB of LDS");
+  static_assert(CPW >= 1 && CPW <= 4, "the staged chunks: at most 16 KB of LDS");
   constexpr int kWaves = kBcastThreads / 64;
   __shared__ float scratch[CPW * kWaves];
   __shared__ double dscratch[CPW * kWaves];
   __shared__ uint32_t other_of_wave[kWaves];
   __shared__ double lane_sum[CPW > 1 ? CPW * kBcastThreads : 1];   // (below: the matrix loop's fold)
-  __shared__ __attribute__((aligned(16))) __bf16 xa[MATRIX ? CPW * kSmemMaxChunk : 8];   // the matrix loop's chunks
+  __shared__ __attribute__((aligned(16))) signed char xa[MATRIX ? CPW * kSmemMaxChunk : 16];   // the matrix loop's chunks
   kernarg_prefetch<(int)sizeof(mi_group)>();
   MI_TL_BEGIN();
   // mode bit 0: rank-one slot layout; bit 1: progress-balanced wave priority (below); bit 2:
@@ -906,10 +918,10 @@ __global__ __launch_bounds__(kBcastThreads) void k_site_bcast_smem(const mi_grou
   // Each lane takes kSmemMaxChunk / kBcastThreads consecutive elements of every chunk (those within
   // it) with all its loads, of all the workgroup's chunks, in flight at once (a strided loop waits
   // for one L2 round trip per element group, at the end of every wave). STAGE: the lane's elements
-  // also go to `xa` as bf16, zeros past the chunk's end. A chunk's sum adds the lane's elements in
+  // also go to `xa` as int8 (one 16-byte write), zeros past the chunk's end. A chunk's sum adds the lane's elements in
   // order from 0, then block_sum's tree: the same bits whatever CPW is.
   constexpr int kPerLane = kSmemMaxChunk / kBcastThreads;
-  static_assert(kPerLane % 8 == 0, "whole float4 groups, and whole 16-byte bf16 groups, per lane");
+  static_assert(kPerLane == 16, "whole float4 groups, and one 16-byte int8 group, per lane");
   float s_a[CPW];
   uint32_t other = 0u;   // bit j: one of this lane's elements of chunk j is neither 0 nor 1
   auto chunk_pass = [&](auto stage_tag) {
@@ -929,7 +941,7 @@ __global__ __launch_bounds__(kBcastThreads) void k_site_bcast_smem(const mi_grou
 #pragma unroll
     for (int j = 0; j < CPW; ++j) {
       const int len = chunk_len(j);
-      __bf16* xj = xa + (STAGE ? j * kSmemMaxChunk : 0);
+      signed char* xj = xa + (STAGE ? j * kSmemMaxChunk : 0);
       float s = 0.0f;
       bool bad = false;
       if (whole[j]) {
@@ -947,13 +959,18 @@ __global__ __launch_bounds__(kBcastThreads) void k_site_bcast_smem(const mi_grou
           s += v[e];
         }
         if (STAGE) {
+          // (1.0f's lowest exponent bit, set, is the int8 one; a chunk with any other value is not
+          // read from the image)
+          i32x4 h;
 #pragma unroll
-          for (int q = 0; q < kPerLane / 8; ++q) {
-            bf16x8 h;
+          for (int q = 0; q < 4; ++q) {
+            uint32_t w = 0u;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) h[e] = (__bf16)v[8 * q + e];
-            reinterpret_cast<bf16x8*>(xj + e0)[q] = h;
+            for (int e = 0; e < 4; ++e)
+              w |= ((__builtin_bit_cast(uint32_t, v[4 * q + e]) >> 23) & 1u) << (8 * e);
+            h[q] = (int)w;
           }
+          *reinterpret_cast<i32x4*>(xj + e0) = h;
         }
       } else if (j < nc) {
         const float* xc = xg + (c0 + j) * chunk;
@@ -962,10 +979,10 @@ __global__ __launch_bounds__(kBcastThreads) void k_site_bcast_smem(const mi_grou
           const float x = xc[e];
           bad |= !(x == 0.0f || x == 1.0f);
           s += x;
-          if (STAGE) xj[e] = (__bf16)x;
+          if (STAGE) xj[e] = x == 1.0f ? 1 : 0;
         }
         if (STAGE)
-          for (int e = max(e0, len); e < e0 + kPerLane; ++e) xj[e] = (__bf16)0.0f;
+          for (int e = max(e0, len); e < e0 + kPerLane; ++e) xj[e] = 0;
       }
       s_a[j] = s;
       other |= bad ? 1u << j : 0u;
@@ -1011,7 +1028,7 @@ __global__ __launch_bounds__(kBcastThreads) void k_site_bcast_smem(const mi_grou
       // A chunk's particle sum in the present order: slots 0, 1 from the first pass, 2, 3 from the
       // second, from 0.0, lanes past K adding nothing. No per-slot totals live through the loop:
       // the lane's running sum of chunk j is a register (CPW = 1) or its own LDS word.
-      // Particle slots per pass: kMatrixP, or one where the pieces have to stay live through a
+      // Particle slots per pass: kMatrixP, or one where the digits have to stay live through a
       // chunk's read-out for the next chunk (CPW > 1: 48 + 48 registers a pass instead of 96 + 96,
       // the chunk read from LDS four times instead of twice).
       constexpr int kPassP = CPW > 1 ? 1 : kMatrixP;
@@ -1022,8 +1039,19 @@ __global__ __launch_bounds__(kBcastThreads) void k_site_bcast_smem(const mi_grou
 #pragma unroll
         for (int j = 0; j < CPW; ++j) lane_sum[j * kBcastThreads + threadIdx.x] = 0.0;
       }
+      // (a 0/1 chunk's sum is its count of ones, exact and at most 4096; 16 bits each of one word,
+      // so that the loop over the chunks indexes no array. A chunk with any other value has a sum
+      // of any size or sign, or none: its field stays zero and is never read.)
+      uint64_t ones = 0u;
+#pragma unroll
+      for (int j = 0; j < CPW; ++j) {
+        const float n1 = ((mat >> j) & 1u) != 0u ? s_a[j] : 0.0f;
+        ones |= (uint64_t)((uint32_t)n1 & 0xffffu) << (16 * j);
+      }
       bcast_matrix_loop<kSmemP, CPW, kPassP>(
-          xa, mat, [&](int j) { return (chunk_len(j) + kFragElems - 1) / kFragElems; }, ld, first_k, K,
+          xa, mat, [&](int j) { return (chunk_len(j) + kFragElems - 1) / kFragElems; },
+          [&](int j) { return (int)((ones >> (16 * j)) & 0xffffu); },
+          ld, first_k, K,
           [&](int j, int p, double total) {
             const int64_t k = kbase + p * kBcastThreads;
             if (p == kPassP - 1) MI_TL(3);
@@ -1800,6 +1828,9 @@ void launch_smem(const mi_group& G, const Plan& p, float* part, uint32_t* flags,
   // element off alignment 41.4 / 38.9, uniform random x 99.6 / 92.5; the shapes that keep one chunk
   // 0.3-0.5 us slower, K 64 n 1e6 16.9 / 17.2, K 256 n 1e6 17.5 / 17.8, K 64 n 1024 14.0 / 14.4,
   // K 4096 n 4096 22.1 / 22.5, K 1024 n 65536 19.7 / 20.2: DESIGN.md section 0q.)
+  // (With the int8 loop, bf16 loop / int8 loop: K 4096 n 1e6 33.3 / 27.3, one element off alignment
+  // 38.9 / 32.8, K 64 n 1e6 17.2 / 16.0, K 256 n 1e6 17.9 / 16.6, K 64 n 1024 14.3 / 13.6, K 4096
+  // n 4096 22.5 / 20.1, K 1024 n 65536 20.2 / 17.8, uniform random x 92.3 / 92.1: section 0r.)
   // Chunks per workgroup (above): 1 launches the grid above; 2 and 4 launch one workgroup per
   // (chunk group, particle block) behind the side job's workgroups, those padded to a multiple of 8.
   else if (env_int("MININF_AMD_BCAST_MFMA", 1) != 0) {
