@@ -1097,6 +1097,54 @@ int mi_gather_site_forward(const mi_gather_site* site, void* workspace, size_t w
                            float* total /* [K] */, const mi_gather_grads* grads /* or NULL */,
                            uint32_t* flags, void* stream);
 
+/* A group-indexed site whose first role also has fixed effects: the varying intercept plus linear
+ * predictor of a multilevel regression,
+ *   eta0[k, i] = shift_k + mult_k * p[k, g_i] + sum_{j < P} X[i, j] * theta[k, j],
+ * role 0 = eta0 (MI_GATHER_LINK_IDENTITY) or exp(eta0) (MI_GATHER_LINK_EXP). `site` is a
+ * mi_gather_site whose role[0] is a GATHER role; role[1] is any kind mi_gather_site takes. X is
+ * read at x[i * x_stride_i + j * x_stride_j] (rows at i = order[j'], like value, mask and DATA
+ * roles), theta at theta[k * theta_stride_k + j * theta_stride_j]. Neither the [K, N] predictor
+ * nor a gradient of its shape exists in memory.
+ *   total, grads: as documented for mi_gather_site, with role 0's eta extended by the linear term
+ *   dtheta[k, j] = g0 * site_scale * sum_i mask_i * (d log p_i / d eta0) * X[i, j]
+ *                  (contiguous [K, P], every entry written; NULL: not wanted), d log p_i / d eta0
+ *                  the per-row quantity summed into role 0's dtable, a link's chain factor included
+ * flags as for mi_gather_site; a non-finite eta0 is a per-row condition here (a non-finite entry
+ * of theta, or of X on an observed row, sets MI_FLAG_PARAM). A masked-out row adds nothing and
+ * sets no flag.
+ *
+ * The layout is mi_gather_site's: a lane owns one particle and walks MI_GATHER_ROWS consecutive
+ * sorted rows, a group's sum stays in the lane, neighbours' parts meet in the workspace in chunk
+ * order. eta0 changes with every row, so the density's terms are derived per row. The lane holds
+ * theta[k, 0..P) and the P sums of dtheta in registers (a float over a batch of 8 rows folded into
+ * a float over the chunk: at most 8 + 32 roundings of a sum), every lane of a particle tile reads
+ * a row of X at one address, and the chunk's P sums leave the lane once, into a workspace slab
+ * [P][chunks][K] that a finishing launch adds in chunk order in fp64. No floating-point atomics:
+ * two calls on the same inputs give the same bits. The workspace is mi_gather_site's plus
+ * K * P * ceil(N / MI_GATHER_ROWS) floats.
+ * MI_EINVAL: those of mi_gather_site, and a role[0] that is not a GATHER role, P < 1, a NULL x or
+ * theta. MI_EUNSUPPORTED: those of mi_gather_site, and P > MI_GATHER_LINEAR_MAX_P (from
+ * mi_gather_linear_workspace_bytes too). MI_EWORKSPACE: a workspace smaller than
+ * mi_gather_linear_workspace_bytes asks for. All checked before any device work. */
+#define MI_GATHER_LINEAR_MAX_P 32
+typedef struct mi_gather_linear {
+  mi_gather_site site;    /* role[0] must be a GATHER role */
+  int64_t P;
+  const float* x;         /* X[i, j] at x[i * x_stride_i + j * x_stride_j] */
+  int64_t x_stride_i;
+  int64_t x_stride_j;
+  const float* theta;     /* theta[k, j] at theta[k * theta_stride_k + j * theta_stride_j] */
+  int64_t theta_stride_k;
+  int64_t theta_stride_j;
+} mi_gather_linear;
+
+int mi_gather_linear_struct_size(size_t* bytes);
+int mi_gather_linear_workspace_bytes(const mi_gather_linear* site, size_t* bytes);
+int mi_gather_linear_forward(const mi_gather_linear* site, void* workspace, size_t workspace_bytes,
+                             float* total /* [K] */, const mi_gather_grads* grads /* or NULL */,
+                             float* dtheta /* [K, P] contiguous or NULL */, uint32_t* flags,
+                             void* stream);
+
 /* ---- device-resident minibatches (replaces examples/minibatch.md:78-88, the host DataLoader) ---- */
 
 /* Row indices of the next minibatch of an n-row dataset: with c = counter[0] (then counter[0] =

@@ -197,6 +197,19 @@ class GatherGrads(ctypes.Structure):
     _fields_ = [("role", c_vp * 2), ("shift", c_vp * 2), ("mult", c_vp * 2)]
 
 
+GATHER_LINEAR_MAX_P = 32   # MI_GATHER_LINEAR_MAX_P
+
+
+class GatherLinear(ctypes.Structure):
+    """mi_gather_linear (include/mininf_amd.h)."""
+    _fields_ = [
+        ("site", GatherSite),
+        ("P", c_i64),
+        ("x", c_vp), ("x_stride_i", c_i64), ("x_stride_j", c_i64),
+        ("theta", c_vp), ("theta_stride_k", c_i64), ("theta_stride_j", c_i64),
+    ]
+
+
 class Source(ctypes.Structure):
     _fields_ = [("ptr", c_vp), ("stride_k", c_i64), ("stride_i", c_i64)]
 
@@ -450,6 +463,12 @@ _SIGNATURES = {
                                                       ctypes.POINTER(ctypes.c_size_t)]),
     "mi_gather_site_forward": (ctypes.c_int, [ctypes.POINTER(GatherSite), c_vp, ctypes.c_size_t,
                                               c_vp, ctypes.POINTER(GatherGrads), c_vp, c_vp]),
+    "mi_gather_linear_struct_size": (ctypes.c_int, [ctypes.POINTER(ctypes.c_size_t)]),
+    "mi_gather_linear_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(GatherLinear),
+                                                        ctypes.POINTER(ctypes.c_size_t)]),
+    "mi_gather_linear_forward": (ctypes.c_int, [ctypes.POINTER(GatherLinear), c_vp, ctypes.c_size_t,
+                                                c_vp, ctypes.POINTER(GatherGrads), c_vp, c_vp,
+                                                c_vp]),
     "mi_minibatch_rows": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, ctypes.c_int32,
                                          ctypes.c_uint64, c_vp, c_i64, c_vp]),
     "mi_gather_rows": (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
@@ -525,6 +544,12 @@ def lib() -> ctypes.CDLL:
         if gather.value != ctypes.sizeof(GatherSite):
             raise NativeError(f"{LIB_PATH} lays mi_gather_site out in {gather.value} bytes, this "
                               f"binding in {ctypes.sizeof(GatherSite)}; rebuild it "
+                              "(mininf_amd/build.py --force).")
+        gather_linear = ctypes.c_size_t()
+        handle.mi_gather_linear_struct_size(ctypes.byref(gather_linear))
+        if gather_linear.value != ctypes.sizeof(GatherLinear):
+            raise NativeError(f"{LIB_PATH} lays mi_gather_linear out in {gather_linear.value} bytes, "
+                              f"this binding in {ctypes.sizeof(GatherLinear)}; rebuild it "
                               "(mininf_amd/build.py --force).")
         _LIB = handle
     return _LIB

@@ -28,110 +28,9 @@
 // Precondition: sorted_group is non-decreasing, its out-of-range entries included (k_gather_tables
 // finds a group's rows by binary search). An unsorted array is never an address out of bounds,
 // but its sums are undefined.
-#include "common.hpp"
-#include "internal.hpp"
+#include "gather_common.hpp"
 
 namespace mi {
-
-constexpr int kGsThreads = 256;
-constexpr int kGsWaves = kGsThreads / kWave;
-constexpr int kGsRows = MI_GATHER_ROWS;
-constexpr int kGsBatch = 8;
-constexpr int kGsMaxSums = 7;   // the value, two PARTICLE roles, two shifts, two mults
-
-// A sum of float terms: a float over a batch of rows, folded into a double.
-struct GsAcc {
-  double hi = 0.0;
-  float lo = 0.0f;
-  __device__ __forceinline__ void add(float x) { lo += x; }
-  __device__ __forceinline__ void fold() {
-    hi += (double)lo;
-    lo = 0.0f;
-  }
-  __device__ __forceinline__ double take() {
-    const double v = hi + (double)lo;
-    hi = 0.0;
-    lo = 0.0f;
-    return v;
-  }
-};
-
-// Where the launch's partial results go (device pointers into the workspace, and the outputs).
-struct GsWork {
-  float* sums;          // [nsum][nchunk][K]
-  float* slab;          // [2 roles][2 ends][nchunk][K]
-  double* rowc;         // [nchunk]: Poisson, the chunk's sum of -lgamma(y + 1)
-  int64_t nchunk;
-  int nsum;
-  int slot_role[2];     // the sum slot of a PARTICLE role, shift, mult; -1: none
-  int slot_shift[2];
-  int slot_mult[2];
-  float* dtable[2];     // GATHER roles' outputs (NULL: not wanted)
-  float* out[kGsMaxSums];   // sum slot -> its [K] output (slot 0: total; NULL: not wanted)
-};
-
-__device__ __forceinline__ bool gs_non_finite(float x) { return !(fabsf(x) < __builtin_inff()); }
-
-__device__ __forceinline__ float gs_value(const mi_gather_site& L, int64_t row) {
-  if (L.value_kind == MI_GATHER_VALUE_INT64)
-    return (float)static_cast<const int64_t*>(L.value)[row * L.value_stride_i];
-  return static_cast<const float*>(L.value)[row * L.value_stride_i];
-}
-
-// What a (group, particle) fixes of the density, and the row's step.
-template <int FAMILY>
-struct GsTerms {
-  float a0, a1;        // the roles after their links
-  float eta0;          // Poisson: log rate
-  float c0, c1, c2;    // per-family invariants
-  bool bad;            // MI_FLAG_PARAM on an observed row
-
-  __device__ __forceinline__ void derive(bool bad_eta) {
-    if constexpr (FAMILY == MI_NORMAL) {
-      const float inv = rcp(a1);
-      c0 = inv;
-      c1 = inv * inv;
-      c2 = -(logf(a1) + kHalfLog2Pi);
-      bad = bad_eta || !(a1 > 0.0f) || (a0 != a0);
-    } else if constexpr (FAMILY == MI_BERNOULLI_LOGITS) {
-      const float t = fast_exp(-fabsf(a0));
-      const float u = 1.0f + t;
-      const float r = rcp(u);
-      c0 = fmaxf(a0, 0.0f) + log1p_unit(t, u, r);   // softplus(l)
-      c1 = a0 >= 0.0f ? r : t * r;                  // sigmoid(l)
-      c2 = 0.0f;
-      bad = bad_eta || (a0 != a0);
-    } else {
-      c0 = c1 = c2 = 0.0f;
-      bad = bad_eta;
-    }
-  }
-
-  // log p and d log p / d role0, d log p / d role1 of a row with value v (Poisson: d / d eta)
-  __device__ __forceinline__ void row(float v, float& lp, float& d0, float& d1) const {
-    if constexpr (FAMILY == MI_NORMAL) {
-      const float diff = v - a0;
-      lp = fmaf((-0.5f * c1) * diff, diff, c2);
-      const float g = diff * c1;
-      d0 = g;
-      d1 = fmaf(diff, g, -1.0f) * c0;
-    } else if constexpr (FAMILY == MI_BERNOULLI_LOGITS) {
-      lp = fmaf(a0, v, -c0);
-      d0 = v - c1;
-      d1 = 0.0f;
-    } else {
-      lp = fmaf(v, eta0, -a0);
-      d0 = v - a0;
-      d1 = 0.0f;
-    }
-  }
-
-  __device__ __forceinline__ static bool unsupported(float v) {
-    if constexpr (FAMILY == MI_NORMAL) return v != v;
-    else if constexpr (FAMILY == MI_BERNOULLI_LOGITS) return !(v == 0.0f || v == 1.0f);
-    else return !(v >= 0.0f && v == floorf(v));
-  }
-};
 
 // Grid: x over blocks of kGsWaves * (64 >> ktl) chunks, y over tiles of 1 << ktl particles.
 template <int FAMILY>
@@ -381,59 +280,24 @@ __global__ __launch_bounds__(256) void k_gather_tables(const mi_gather_site L, c
   *dst = (float)(gscale * (double)mult * S);
 }
 
-}  // namespace mi
-
-namespace {
-
-bool valid_role(const mi_gather_role& R) {
-  if (R.kind < MI_GATHER_CONSTANT || R.kind > MI_GATHER_DATA) return false;
-  if (R.kind != MI_GATHER_CONSTANT && R.data == nullptr) return false;
-  if (R.link != MI_GATHER_LINK_IDENTITY && R.link != MI_GATHER_LINK_EXP) return false;
-  if (R.shift_kind < MI_GATHER_TERM_NONE || R.shift_kind > MI_GATHER_TERM_CONSTANT) return false;
-  if (R.mult_kind < MI_GATHER_TERM_NONE || R.mult_kind > MI_GATHER_TERM_CONSTANT) return false;
-  if (R.shift_kind == MI_GATHER_TERM_PARTICLE && R.shift == nullptr) return false;
-  if (R.mult_kind == MI_GATHER_TERM_PARTICLE && R.mult == nullptr) return false;
-  return true;
-}
-
-bool valid(const mi_gather_site* L) {
-  return L != nullptr && L->K >= 1 && L->N >= 1 && L->G >= 1 &&
-         (L->family == MI_NORMAL || L->family == MI_BERNOULLI_LOGITS || L->family == MI_POISSON) &&
-         valid_role(L->role[0]) && valid_role(L->role[1]) &&
-         (L->role[0].kind == MI_GATHER_GATHER || L->role[1].kind == MI_GATHER_GATHER) &&
-         L->order != nullptr && L->sorted_group != nullptr && L->value != nullptr &&
-         (L->value_kind == MI_GATHER_VALUE_FLOAT32 || L->value_kind == MI_GATHER_VALUE_INT64);
-}
-
-// The sum slots a site has (whatever gradients a call asks for) and the workspace's parts.
-struct Layout {
-  int64_t nchunk;
-  int nsum;
-  int slot_role[2], slot_shift[2], slot_mult[2];
-  size_t sums_bytes, slab_bytes, rowc_bytes;
-};
-
-size_t round256(size_t n) { return (n + 255) / 256 * 256; }
-
-Layout layout(const mi_gather_site* L) {
-  Layout y{};
-  y.nchunk = ceil_div(L->N, mi::kGsRows);
-  y.nsum = 1;
-  for (int r = 0; r < 2; ++r) {
-    const mi_gather_role& R = L->role[r];
-    const bool gather = R.kind == MI_GATHER_GATHER;
-    y.slot_role[r] = R.kind == MI_GATHER_PARTICLE ? y.nsum++ : -1;
-    y.slot_shift[r] = gather && R.shift_kind == MI_GATHER_TERM_PARTICLE ? y.nsum++ : -1;
-    y.slot_mult[r] = gather && R.mult_kind == MI_GATHER_TERM_PARTICLE ? y.nsum++ : -1;
+// (gather_common.hpp)
+int gs_finish(const mi_gather_site* site, const GsWork& W, double gscale, const int table_roles[2],
+              int ntables, hipStream_t s) {
+  hipError_t e;
+  hipLaunchKernelGGL(k_gather_sums, dim3((unsigned)ceil_div(site->K, 32), (unsigned)W.nsum),
+                     dim3(32 * kGsParts), 0, s, W, site->K, site->site_scale, gscale,
+                     site->family == MI_POISSON ? 1 : 0);
+  if ((e = hipGetLastError()) != hipSuccess) return to_code(e);
+  if (ntables > 0) {
+    hipLaunchKernelGGL(k_gather_tables,
+                       dim3((unsigned)ceil_div(site->G, 256), (unsigned)site->K, (unsigned)ntables),
+                       dim3(256), 0, s, *site, W, gscale, table_roles[0], table_roles[ntables - 1]);
+    if ((e = hipGetLastError()) != hipSuccess) return to_code(e);
   }
-  const size_t plane = (size_t)y.nchunk * (size_t)L->K * sizeof(float);
-  y.sums_bytes = round256(plane * (size_t)y.nsum);
-  y.slab_bytes = round256(plane * 4);
-  y.rowc_bytes = round256((size_t)y.nchunk * sizeof(double));
-  return y;
+  return 0;
 }
 
-}  // namespace
+}  // namespace mi
 
 extern "C" {
 
@@ -444,60 +308,30 @@ int mi_gather_site_struct_size(size_t* bytes) {
 }
 
 int mi_gather_site_workspace_bytes(const mi_gather_site* site, size_t* bytes) {
-  if (!valid(site) || bytes == nullptr) return MI_EINVAL;
-  const Layout y = layout(site);
-  *bytes = y.sums_bytes + y.slab_bytes + y.rowc_bytes;
+  if (!mi::gs_valid(site) || bytes == nullptr) return MI_EINVAL;
+  *bytes = mi::gs_layout(site).bytes();
   return 0;
 }
 
 int mi_gather_site_forward(const mi_gather_site* site, void* workspace, size_t workspace_bytes,
                            float* total, const mi_gather_grads* grads, uint32_t* flags,
                            void* stream) {
-  if (!valid(site) || total == nullptr || flags == nullptr) return MI_EINVAL;
-  const Layout y = layout(site);
-  int ktl = 0;
-  while (ktl < 6 && (1 << ktl) < site->K) ++ktl;
-  const int64_t gy = ceil_div(site->K, (int64_t)1 << ktl);
-  const int64_t gx = ceil_div(y.nchunk, (int64_t)mi::kGsWaves * (mi::kWave >> ktl));
-  // a Poisson rate is exp of a gathered predictor; grids within the launch limits
-  if (site->family == MI_POISSON &&
-      !(site->role[0].kind == MI_GATHER_GATHER && site->role[0].link == MI_GATHER_LINK_EXP))
-    return MI_EUNSUPPORTED;
-  if (gx > kMaxGrid || gy > 65535 || site->K > 65535 || ceil_div(site->G, 256) > kMaxGrid ||
-      site->N > 0x7FFFFFFF)
-    return MI_EUNSUPPORTED;
-  const size_t need = y.sums_bytes + y.slab_bytes + y.rowc_bytes;
-  if (workspace == nullptr || workspace_bytes < need) return MI_EWORKSPACE;
+  if (!mi::gs_valid(site) || total == nullptr || flags == nullptr) return MI_EINVAL;
+  const mi::GsLayout y = mi::gs_layout(site);
+  const mi::GsGrid g = mi::gs_grid(site, y);
+  if (!mi::gs_supported(site, g)) return MI_EUNSUPPORTED;
+  if (workspace == nullptr || workspace_bytes < y.bytes()) return MI_EWORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipError_t e;
   if (!(site->options & MI_GROUP_FLAGS_ZEROED)) {
     if ((e = hipMemsetAsync(flags, 0, sizeof(uint32_t), s)) != hipSuccess) return to_code(e);
   }
   mi::GsWork W{};
-  char* base = static_cast<char*>(workspace);
-  W.sums = reinterpret_cast<float*>(base);
-  W.slab = reinterpret_cast<float*>(base + y.sums_bytes);
-  W.rowc = reinterpret_cast<double*>(base + y.sums_bytes + y.slab_bytes);
-  W.nchunk = y.nchunk;
-  W.nsum = y.nsum;
-  W.out[0] = total;
-  int table_roles[2] = {0, 0}, ntables = 0;
-  for (int r = 0; r < 2; ++r) {
-    W.slot_role[r] = y.slot_role[r];
-    W.slot_shift[r] = y.slot_shift[r];
-    W.slot_mult[r] = y.slot_mult[r];
-    const bool gather = site->role[r].kind == MI_GATHER_GATHER;
-    // (a Bernoulli or Poisson site has no second role: nothing of it is written)
-    const bool live = r == 0 || site->family == MI_NORMAL;
-    float* out = grads != nullptr && live ? grads->role[r] : nullptr;
-    W.dtable[r] = gather ? out : nullptr;
-    if (W.dtable[r] != nullptr) table_roles[ntables++] = r;
-    if (y.slot_role[r] >= 0) W.out[y.slot_role[r]] = out;
-    if (y.slot_shift[r] >= 0) W.out[y.slot_shift[r]] = grads != nullptr && live ? grads->shift[r] : nullptr;
-    if (y.slot_mult[r] >= 0) W.out[y.slot_mult[r]] = grads != nullptr && live ? grads->mult[r] : nullptr;
-  }
+  int table_roles[2];
+  const int ntables = mi::gs_bind(site, y, workspace, total, grads, W, table_roles);
   const double gscale = (double)site->grad_scale * site->site_scale;
-  const dim3 grid((unsigned)gx, (unsigned)gy);
+  const dim3 grid((unsigned)g.gx, (unsigned)g.gy);
+  const int ktl = g.ktl;
   if (site->family == MI_NORMAL)
     hipLaunchKernelGGL((mi::k_gather_site<MI_NORMAL>), grid, dim3(mi::kGsThreads), 0, s, *site, W, ktl,
                        gscale, flags);
@@ -508,17 +342,7 @@ int mi_gather_site_forward(const mi_gather_site* site, void* workspace, size_t w
     hipLaunchKernelGGL((mi::k_gather_site<MI_POISSON>), grid, dim3(mi::kGsThreads), 0, s, *site, W, ktl,
                        gscale, flags);
   if ((e = hipGetLastError()) != hipSuccess) return to_code(e);
-  hipLaunchKernelGGL(mi::k_gather_sums, dim3((unsigned)ceil_div(site->K, 32), (unsigned)y.nsum),
-                     dim3(32 * mi::kGsParts), 0, s, W, site->K, site->site_scale, gscale,
-                     site->family == MI_POISSON ? 1 : 0);
-  if ((e = hipGetLastError()) != hipSuccess) return to_code(e);
-  if (ntables > 0) {
-    hipLaunchKernelGGL(mi::k_gather_tables,
-                       dim3((unsigned)ceil_div(site->G, 256), (unsigned)site->K, (unsigned)ntables),
-                       dim3(256), 0, s, *site, W, gscale, table_roles[0], table_roles[ntables - 1]);
-    if ((e = hipGetLastError()) != hipSuccess) return to_code(e);
-  }
-  return 0;
+  return mi::gs_finish(site, W, gscale, table_roles, ntables, s);
 }
 
 }  // extern "C"

@@ -431,7 +431,9 @@ class _ElboPlan:
         (mi_elementwise_rsample); lowrank_entropies: LowRankMultivariateNormal guide factors whose
         entropy and its gradient the native kernel evaluated (mi_lowrank_entropy, called by the
         loss after this plan ran); gathered_sites: sites on the model's own ``alpha[group]`` that
-        this evaluation ran on mi_gather_site_forward (no [K, N] gather, no scatter-add).
+        this evaluation ran on a gather kernel (no [K, N] gather, no scatter-add);
+        gathered_linear_sites: those of them with fixed effects, ``alpha[group] + X @ theta``, on
+        mi_gather_linear_forward (no [K, N] product either).
         """
         return {
             "folded_priors": sum(l.prior is not None for l in self.launchers) +
@@ -451,6 +453,9 @@ class _ElboPlan:
             "lowrank_entropies": 0,   # set by the loss, which evaluates the rest's entropies
             "gathered_sites": sum(site.gather is not None and site.gather.launches > 0
                                   for site, _, _, _ in self.categorical),
+            "gathered_linear_sites": sum(site.gather is not None and site.gather.linear and
+                                         site.gather.launches > 0
+                                         for site, _, _, _ in self.categorical),
         }
 
     def _reduce_ok(self, assume=None) -> bool:

@@ -1,7 +1,9 @@
 """
 Group-indexed sites: Normal / Bernoulli-logits / Poisson sites whose parameter is the model's own
 gather ``alpha[group]`` of a per-particle table [K, G], fused (``mi_gather_site_forward``; the
-gather was deferred by :mod:`mininf_amd.linear`). Such a site is planned as a row site -- an entry
+gather was deferred by :mod:`mininf_amd.linear`), and those whose first role also has fixed
+effects, ``alpha[group] + X @ theta`` (``mi_gather_linear_forward``: theta [K, P] joins the
+launcher's parameters). Such a site is planned as a row site -- an entry
 (site, parameters, value, mask) of the planner's categorical list whose record carries its launcher
 (``site.gather``) -- so the ELBO plan, ``log_joint`` and ``LogLikelihoodLoss`` take it like any row
 site: its speculative gradients are dense in every parameter (the tables [K, G], per-particle
@@ -83,6 +85,9 @@ class _Role:
         self.mult = None
         # positions among the launcher's parameters (autograd inputs), or -1
         self.param = self.shift_param = self.mult_param = -1
+        # role 0's linear term: the observed X [N, P] and theta's position among the parameters
+        self.X: Optional[torch.Tensor] = None
+        self.theta_param = -1
 
 
 class _GatherLauncher:
@@ -96,7 +101,19 @@ class _GatherLauncher:
         self.N, self.G = int(order.shape[0]), G
         self.value = value            # [N] float32 or int64
         self.mask = mask              # [N] bool or None
-        self.launches = 0             # mi_gather_site_forward calls that ran (not declined)
+        self.launches = 0             # kernel calls that ran (not declined)
+        self.linear = roles[0].X is not None   # mi_gather_linear_forward
+
+    def describe_linear(self, params: Tuple[torch.Tensor, ...], g0: float) -> nat.GatherLinear:
+        M = nat.GatherLinear()
+        M.site = self.describe(params, g0)
+        X, theta = self.roles[0].X, params[self.roles[0].theta_param]
+        M.P = int(X.shape[1])
+        M.x = X.data_ptr()
+        M.x_stride_i, M.x_stride_j = X.stride()
+        M.theta = theta.data_ptr()
+        M.theta_stride_k, M.theta_stride_j = theta.stride()
+        return M
 
     def describe(self, params: Tuple[torch.Tensor, ...], g0: float) -> nat.GatherSite:
         L = nat.GatherSite()
@@ -147,9 +164,11 @@ class _GatherLauncher:
         """(total [K], the speculative gradients of ``params`` -- None where none is needed --,
         flags [1])."""
         device = self.device
-        L = self.describe(params, g0)
+        L = self.describe_linear(params, g0) if self.linear else self.describe(params, g0)
         if flags is None:
             flags = torch.empty(1, dtype=torch.int32, device=device)
+        elif self.linear:
+            L.site.options |= nat.GROUP_FLAGS_ZEROED
         else:
             L.options |= nat.GROUP_FLAGS_ZEROED
         grads: List[Optional[torch.Tensor]] = [None] * len(params)
@@ -164,16 +183,32 @@ class _GatherLauncher:
                     field[r] = grads[where].data_ptr()
         size = ctypes.c_size_t()
         lib = nat.lib()
-        nat.check(lib.mi_gather_site_workspace_bytes(ctypes.byref(L), ctypes.byref(size)),
-                  "mi_gather_site_workspace_bytes")
-        workspace = torch.empty(max(1, size.value), dtype=torch.uint8, device=device)
         total = torch.empty(self.K, dtype=torch.float32, device=device)
-        code = lib.mi_gather_site_forward(ctypes.byref(L), workspace.data_ptr(), size.value,
-                                          total.data_ptr(), ctypes.byref(G), flags.data_ptr(),
-                                          nat.stream_handle(device))
+        if self.linear:
+            where = self.roles[0].theta_param
+            dtheta = None
+            if params[where].requires_grad:   # [K, P] contiguous, every entry written
+                grads[where] = torch.empty(tuple(params[where].shape), dtype=torch.float32,
+                                           device=device)
+                dtheta = grads[where].data_ptr()
+            code = lib.mi_gather_linear_workspace_bytes(ctypes.byref(L), ctypes.byref(size))
+            if code == nat.MI_EUNSUPPORTED:
+                return self._materialised(params, g0, flags)
+            nat.check(code, "mi_gather_linear_workspace_bytes")
+            workspace = torch.empty(max(1, size.value), dtype=torch.uint8, device=device)
+            code = lib.mi_gather_linear_forward(ctypes.byref(L), workspace.data_ptr(), size.value,
+                                                total.data_ptr(), ctypes.byref(G), dtheta,
+                                                flags.data_ptr(), nat.stream_handle(device))
+        else:
+            nat.check(lib.mi_gather_site_workspace_bytes(ctypes.byref(L), ctypes.byref(size)),
+                      "mi_gather_site_workspace_bytes")
+            workspace = torch.empty(max(1, size.value), dtype=torch.uint8, device=device)
+            code = lib.mi_gather_site_forward(ctypes.byref(L), workspace.data_ptr(), size.value,
+                                              total.data_ptr(), ctypes.byref(G), flags.data_ptr(),
+                                              nat.stream_handle(device))
         if code == nat.MI_EUNSUPPORTED:
             return self._materialised(params, g0, flags)
-        nat.check(code, "mi_gather_site_forward")
+        nat.check(code, "mi_gather_linear_forward" if self.linear else "mi_gather_site_forward")
         self.launches += 1
         return total, tuple(grads), flags
 
@@ -189,9 +224,10 @@ class _GatherLauncher:
             return tensor.reshape(1, self.N)
         index = torch.empty(self.N, dtype=torch.int64, device=self.device)
         index[self.order.long()] = self.sorted_group.long()
+        linear = params[role.theta_param] @ role.X.t() if role.X is not None else None
         return _affine(tensor[:, index], params[role.shift_param] if role.shift_param >= 0
                        else role.shift, params[role.mult_param] if role.mult_param >= 0
-                       else role.mult, role.link == nat.GATHER_LINK_EXP)
+                       else role.mult, role.link == nat.GATHER_LINK_EXP, linear)
 
     def _materialised(self, params: Tuple[torch.Tensor, ...], g0: float, flags: torch.Tensor):
         """The launch the library declined, through torch on the materialised gather."""
@@ -217,13 +253,16 @@ class _GatherLauncher:
         return total.detach(), grads, flags
 
 
-def _affine(gathered: torch.Tensor, shift, mult, exp: bool) -> torch.Tensor:
-    """link(shift + mult * gathered) for [K, N] ``gathered`` and None / number / [K] terms."""
+def _affine(gathered: torch.Tensor, shift, mult, exp: bool, linear=None) -> torch.Tensor:
+    """link(shift + mult * gathered [+ linear]) for [K, N] ``gathered`` (and ``linear``) and None /
+    number / [K] terms."""
     K = gathered.shape[0]
     if mult is not None:
         gathered = (mult.reshape(K, 1) if isinstance(mult, torch.Tensor) else mult) * gathered
     if shift is not None:
         gathered = (shift.reshape(K, 1) if isinstance(shift, torch.Tensor) else shift) + gathered
+    if linear is not None:
+        gathered = gathered + linear
     return gathered.exp() if exp else gathered
 
 
@@ -265,6 +304,17 @@ def plan_gather(site: SiteRecord, K: int, device: torch.device):
         all(not isinstance(t, torch.Tensor) or (t.dtype == torch.float32 and t.device == device and
                                                 t.numel() == K)
             for t in (g.shift, g.mult)) for g in live)
+    # a linear term: float32 X [N, P] and theta [K, P] on the device, X held whole (not a
+    # DeviceDataLoader column), P within the kernel's registers
+    for g in live:
+        if g.linear_X is not None:
+            X, theta = g.linear_X, g.linear_theta
+            ok = ok and g is site.gather_roles[0] and len(live) == 1 and \
+                X.dtype == torch.float32 and X.device == device and not X.requires_grad and \
+                X.dim() == 2 and X.shape[0] == N and \
+                1 <= X.shape[1] <= nat.GATHER_LINEAR_MAX_P and data.lookup(X) is None and \
+                theta.dtype == torch.float32 and theta.device == device and \
+                tuple(theta.shape) == (K, X.shape[1])
     G = int(live[0].table.shape[1]) if ok else 0
     ok = ok and all(int(g.table.shape[1]) == G for g in live)
     ok_index = ok
@@ -291,6 +341,10 @@ def plan_gather(site: SiteRecord, K: int, device: torch.device):
                     setattr(role, name + "_param", len(params))
                     params.append(term.reshape(K))
                 setattr(role, name, term)
+            if g.linear_X is not None:
+                role.X = g.linear_X
+                role.theta_param = len(params)
+                params.append(g.linear_theta)
             roles.append(role)
             continue
         t, constant = _to_device(site.tensors[r], K, device, f"site '{site.name}'")

@@ -26,6 +26,7 @@ call                                  kind    link of ``ph``         new link
 broadcasting views                    either  any                    unchanged
 ``exp(ph)``                           either  identity               exp
 ``ph + c``, ``ph - c``, ``ph * c``    gather  identity               identity
+``gather + matmul`` (``defer_sum``)   both    identity, identity     identity
 ``ph.logsumexp(-1, keepdim=True)``    matmul  identity, log_softmax  logsumexp
 ``log_softmax(ph, -1)``               matmul  identity, log_softmax  log_softmax
 ``ph - lse``                          matmul  identity, log_softmax  log_softmax
@@ -36,6 +37,12 @@ plain and the reflected forms: they compose ``shift + mult * table[index]``. The
 a [.., N, C] placeholder of ``X @ Theta`` and are how ``Categorical.__init__`` normalises its logits
 (``logits - logits.logsumexp(dim=-1, keepdim=True)``: ``lse`` is the logsumexp placeholder of the
 same root after the same normalisations) and how a model does (``torch.log_softmax(eta, -1)``).
+With ``defer_sum`` the sum (``add`` in all its forms, either order) of a gather placeholder with any
+affine chain and the root placeholder of ``X @ theta`` for a vector ``theta`` of at most
+``MAX_SUM_FEATURES`` entries over the same N is a gather-kind record that also carries ``X``,
+``theta`` and which operand stood on the left (``mi_gather_linear_forward``). It still takes
+``+ c``, ``- c`` (composed into ``shift``, remembered in ``post``) and ``exp``; ``* c`` and ``c - ...``
+(which would negate the linear term) materialise, like a second gather or product.
 Metadata queries and ``x.type_as(ph)`` read no values and pass a placeholder through.
 
 **Anything else materialises.** Every other torch operation that meets a placeholder first gets its
@@ -94,6 +101,8 @@ _ARITHMETIC = {"add": _ADDS, "sub": _SUBS, "mul": _MULS}
 
 # Most categories of a deferred `X @ Theta` (MI_SOFTMAX_LINEAR_MAX_C of include/mininf_amd.h).
 MAX_CATEGORIES = 32
+# Most columns of X in a deferred ``alpha[group] + X @ theta`` (MI_GATHER_LINEAR_MAX_P).
+MAX_SUM_FEATURES = 32
 
 
 class NeedsDraws(Exception):
@@ -140,10 +149,12 @@ class Deferred:
     (``x - x.logsumexp(-1, keepdim=True)``) or "log_softmax". Every derived record hangs off its
     root: its replay is the whole path from the product.
 
-    ``"gather"``: ``link(shift + mult * table[index])`` with ``shift`` / ``mult`` None (0 / 1), a
+    ``"gather"``: ``link(shift + mult * table[index] [+ X @ theta])`` with ``shift`` / ``mult`` None (0 / 1), a
     Python number or a per-particle (batched 0-d) tensor. ``chain`` lists the affine operations, in
     order, for :func:`put_back`: ("add" | "sub" | "mul", c, left), the placeholder the left
-    operand or not.
+    operand or not. After a deferred sum ``X`` and ``theta`` are the product's, ``linear_left``
+    says whether the gather was the sum's left operand and ``post`` lists the later scalar
+    operations like ``chain``.
     """
     kind: str
     shape: torch.Size
@@ -159,6 +170,8 @@ class Deferred:
     shift: Any = None
     mult: Any = None
     chain: Tuple[Tuple[str, Any, bool], ...] = ()
+    linear_left: bool = True
+    post: Tuple[Tuple[str, Any, bool], ...] = ()
 
     @property
     def root(self) -> "Deferred":
@@ -197,12 +210,14 @@ class DeferredMatmul(TorchFunctionMode):
     require_device = True   # defer only device operands (the fused kernels')
 
     def __init__(self, K: int, defer_matmul: bool = True,
-                 defer_gather: Optional[bool] = None) -> None:
+                 defer_gather: Optional[bool] = None, defer_sum: bool = False) -> None:
         super().__init__()
         self.K = K
         self.defer_matmul = defer_matmul
         self.defer_gather = switches.enabled("DEFER_GATHER") if defer_gather is None \
             else defer_gather
+        # (the sum of both predictors needs both deferred)
+        self.defer_sum = bool(defer_sum and self.defer_matmul and self.defer_gather)
         self.deferred: Dict[int, Deferred] = {}   # id(placeholder) -> its record
         # per-particle scalars broadcast beside a gather placeholder (Normal's broadcast_all of
         # loc and scale): the broadcast view -> the scalar it came from
@@ -214,11 +229,11 @@ class DeferredMatmul(TorchFunctionMode):
     @contextlib.contextmanager
     def _bypassed(self):
         """Torch calls made inside run as they are (the mode's own calls on real tensors)."""
-        self._bypass = True
+        previous, self._bypass = self._bypass, True
         try:
             yield
         finally:
-            self._bypass = False
+            self._bypass = previous
 
     def lookup(self, tensor: Any, kind: Optional[str] = None) -> Optional[Deferred]:
         """The record of a placeholder (of ``kind``, if given), or None."""
@@ -364,6 +379,9 @@ class DeferredMatmul(TorchFunctionMode):
         info = self._accepted(ph, "gather", ("identity",))
         if info is None:
             return None
+        summed = info.X is not None
+        if summed and (op == "mul" or (op == "sub" and not left)):
+            return None   # (the kernel's linear term has no factor of its own)
         shift, mult = info.shift, info.mult
         with self._bypassed():   # (per-particle scalars: [K] operations)
             if op == "add":
@@ -380,8 +398,34 @@ class DeferredMatmul(TorchFunctionMode):
         def replay(real):
             operands = (real, c) if left else (c, real)
             return func(*(operands[::-1] if reflected else operands))
+        if summed:
+            return info.derived(shift=shift, mult=mult, replay=replay,
+                                post=info.post + ((op, c, left),))
         return info.derived(shift=shift, mult=mult, replay=replay,
                             chain=info.chain + ((op, c, left),))
+
+    def _sum(self, func: Callable, args, kwargs) -> Optional[Deferred]:
+        """``gather + matmul`` in either order (``defer_sum``): an identity-link gather placeholder
+        with any affine chain and the identity-link root of ``X @ theta`` for a vector ``theta``,
+        both over the same N."""
+        if not self.defer_sum or func not in _ADDS or kwargs or len(args) != 2:
+            return None
+        x, y = (args[1], args[0]) if _ADDS[func] else args   # the call computes x + y
+        left = self.lookup(x, "gather") is not None
+        g = self._accepted(x if left else y, "gather", ("identity",))
+        m = self._accepted(y if left else x, "matmul", ("identity",))
+        if g is None or m is None or g.X is not None or m.parent is not None or \
+                m.theta.dim() != 1 or m.theta.shape[0] > MAX_SUM_FEATURES or \
+                tuple(g.shape) != tuple(m.shape) or len(g.shape) != 1 or \
+                m.X.device != g.table.device:
+            return None
+
+        def replay(real):
+            product = self._real(m)
+            with self._bypassed():
+                operands = (real, product) if left else (product, real)
+                return func(*(operands[::-1] if _ADDS[func] else operands))
+        return g.derived(X=m.X, theta=m.theta, linear_left=left, replay=replay)
 
     def _softmax_operand(self, args) -> Optional[Deferred]:
         """The record of ``args[0]`` if a softmax normalisation may derive from it: a [.., N, C]
@@ -417,7 +461,7 @@ class DeferredMatmul(TorchFunctionMode):
         return _matmul_derived(info.root, info.shape, "log_softmax", info.steps + ("sub",))
 
     # tried in this order; a call none of them accepts materialises its placeholders
-    _DERIVATIONS = (_exp, _affine, _logsumexp, _log_softmax, _sub_logsumexp)
+    _DERIVATIONS = (_exp, _affine, _sum, _logsumexp, _log_softmax, _sub_logsumexp)
 
     # ---- the mode ----------------------------------------------------------------------------
     def __torch_function__(self, func: Callable, types, args=(), kwargs=None):
@@ -509,6 +553,17 @@ def put_back(site, K: int) -> None:
                     real = real - c if left else c - real
                 else:
                     real = real * c if left else c * real
+            if g.linear_X is not None:
+                # the product as put_back spells a vector regression, the sum in the model's
+                # operand order, then the later scalar operations
+                product = g.linear_theta @ g.linear_X.t()
+                real = real + product if g.linear_left else product + real
+                for op, c, left in g.post:
+                    c = c.reshape(K, 1) if isinstance(c, torch.Tensor) else c
+                    if op == "add":
+                        real = real + c if left else c + real
+                    else:
+                        real = real - c
             site.tensors[r] = real.exp() if g.link == "exp" else real
         site.gather_roles = None
         return

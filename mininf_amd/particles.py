@@ -142,6 +142,14 @@ class GatherRole:
     # Python number or (an output index, after tracing a [K] tensor) and the gather the left
     # operand or not; shift and mult are their composition
     chain: List[Tuple[str, Any, bool]] = dataclasses.field(default_factory=list)
+    # role 0 of a multilevel regression, link(shift + mult * table[:, index] + X @ theta): the
+    # observed X [N, P], theta (an output index; after tracing [K, P]), whether the gather was the
+    # sum's left operand and the scalar operations after the sum (like ``chain``)
+    linear_X: Optional[torch.Tensor] = None
+    linear_theta_output: int = -1
+    linear_theta: Optional[torch.Tensor] = None
+    linear_left: bool = True
+    post: List[Tuple[str, Any, bool]] = dataclasses.field(default_factory=list)
 
 
 @dataclasses.dataclass
@@ -613,7 +621,11 @@ class ParticleTracer(TracerMixin):
                 mult_output=self._emit(g.mult) if isinstance(g.mult, torch.Tensor) else -1,
                 shift=g.shift, mult=g.mult,
                 chain=[(op, ("output", self._emit(c)) if isinstance(c, torch.Tensor) else c, left)
-                       for op, c, left in g.chain]) for g in gathered]
+                       for op, c, left in g.chain],
+                linear_X=g.X, linear_theta_output=self._emit(g.theta) if g.X is not None else -1,
+                linear_left=g.linear_left,
+                post=[(op, ("output", self._emit(c)) if isinstance(c, torch.Tensor) else c, left)
+                      for op, c, left in g.post]) for g in gathered]
         self.sites.append(record)
         return value
 
@@ -689,6 +701,10 @@ class ParticleTracer(TracerMixin):
         if is_batched(data) or tuple(data.shape) != (N,) or tuple(shape) != (N,):
             return None
         if any(mode.lookup(p, "matmul") is not None for p in params):
+            return None
+        # a deferred sum is role 0 and the site's only gathered role (a gathered scale beside
+        # it materialises)
+        if any(info.X is not None for info in live) and (len(live) > 1 or infos[0] is None):
             return None
         return infos
 
@@ -819,29 +835,30 @@ _NO_VALIDATE = object()
 
 def trace_particles(model: Callable, samples: Dict[str, torch.Tensor], K: int,
                     validate: bool = True, defer_matmul: Optional[bool] = None,
-                    lift_host: bool = False) -> ParticleTrace:
+                    lift_host: bool = False, defer_sum: bool = False) -> ParticleTrace:
     """
     Run ``condition(model, **samples)`` once under ``vmap`` over the leading (particle) dimension of
     every sample and return the recorded sites with [K, ...] tensors. With ``defer_matmul``,
     ``X @ theta`` predictors of Normal / Bernoulli-logits sites are evaluated inside the site
     kernels instead of by the model (:mod:`mininf_amd.linear`). A model that mixes its own host
     tensors with the device particles, or factorises a matrix, is traced again under
-    :class:`TraceCompat`.
+    :class:`TraceCompat`. With ``defer_sum`` (and both deferrals on) the sum
+    ``alpha[group] + X @ theta`` is recorded as one gathered site with a linear term.
     """
     device = next((t.device for t in samples.values() if isinstance(t, torch.Tensor)), None)
     lift = device if device is not None and device.type != "cpu" else None
     if not lift_host:
         try:
-            return _trace(model, samples, K, validate, defer_matmul, False, None)
+            return _trace(model, samples, K, validate, defer_matmul, False, None, defer_sum)
         except RuntimeError as error:
             if not _needs_compat(error):
                 raise
-    return _trace(model, samples, K, validate, defer_matmul, True, lift)
+    return _trace(model, samples, K, validate, defer_matmul, True, lift, defer_sum)
 
 
 def _trace(model: Callable, samples: Dict[str, torch.Tensor], K: int, validate: bool,
            defer_matmul: Optional[bool], compat: bool,
-           lift: Optional[torch.device]) -> ParticleTrace:
+           lift: Optional[torch.device], defer_sum: bool = False) -> ParticleTrace:
     from .linear import DeferredMatmul
 
     if defer_matmul is None:
@@ -856,7 +873,7 @@ def _trace(model: Callable, samples: Dict[str, torch.Tensor], K: int, validate: 
         flush_draws()   # no mode watches the model's reads of deferred guide draws
 
     def per_particle(*values):
-        mode = DeferredMatmul(K, defer_matmul, defer_gather) if use_mode else None
+        mode = DeferredMatmul(K, defer_matmul, defer_gather, defer_sum) if use_mode else None
         tracer.deferred = mode
         with tracer, contextlib.ExitStack() as stack:
             if lift is not None:
@@ -896,6 +913,10 @@ def _trace(model: Callable, samples: Dict[str, torch.Tensor], K: int, validate: 
                     g.mult = outputs[g.mult_output]
                 g.chain = [(op, outputs[c[1]] if isinstance(c, tuple) else c, left)
                            for op, c, left in g.chain]
+                if g.linear_theta_output >= 0:
+                    g.linear_theta = outputs[g.linear_theta_output]
+                g.post = [(op, outputs[c[1]] if isinstance(c, tuple) else c, left)
+                          for op, c, left in g.post]
     checks = [(check, outputs[check.output]) for check in tracer.checks]
     fallback = [(name, outputs[index]) for name, index in tracer.fallback_outputs]
     return ParticleTrace(sites=tracer.sites, checks=checks, fallback=fallback, K=K)
