@@ -1145,6 +1145,61 @@ int mi_gather_linear_forward(const mi_gather_linear* site, void* workspace, size
                              float* dtheta /* [K, P] contiguous or NULL */, uint32_t* flags,
                              void* stream);
 
+/* A group-indexed site with varying slopes: the predictor of role 0 is
+ *   eta0[k, i] = shift_k + mult_k * p[k, g_i] + sum_{s < S} beta_s[k, g_i] * z_s[i]
+ *              + sum_{j < P} X[i, j] * theta[k, j],
+ * 1 <= S <= MI_GATHER_MAX_SLOPES slope terms, each a per-particle table beta_s [K, G] gathered by
+ * the site's index (slope[s].table[k * stride_k + g * stride_g]) times an observed float32 column
+ * z_s [N] (slope[s].z[i * z_stride_i], rows at i = order[j'] like value, mask and X), and
+ * 0 <= P <= MI_GATHER_LINEAR_MAX_P fixed effects (`linear`, a mi_gather_linear whose P may be 0: x
+ * and theta are then not read and may be NULL). Families, links, role 1, mask, values, site_scale
+ * and grad_scale are mi_gather_linear's. eta0 is evaluated in float32 in a fixed order:
+ * fmaf(mult, p, shift), one fmaf(beta_s, z_s, eta) per slope s = 0..S-1, one fmaf(X[i, j],
+ * theta[j], eta) per column j = 0..P-1.
+ *   total, grads, dtheta: as documented for mi_gather_linear, with the slope terms inside eta0
+ *                  (dtheta is not touched when P = 0)
+ *   dslope[s][k, g] = g0 * site_scale * sum_{i in g} mask_i * (d log p_i / d eta0) * z_s[i]
+ *                  (contiguous [K, G], every entry written, a group without rows exactly 0; a NULL
+ *                  entry, or a NULL array, is not wanted), d log p_i / d eta0 the per-row quantity
+ *                  summed into role 0's dtable and into dtheta
+ * flags as for mi_gather_linear: a non-finite beta_s entry of a group with an observed row, or a
+ * non-finite z_s on an observed row, sets MI_FLAG_PARAM through the non-finite eta0. A masked-out
+ * row reads no z, adds nothing and sets no flag.
+ *
+ * The layout is mi_gather_linear's. A lane loads beta_s[k, g] when the group changes and keeps one
+ * more sum per slope (a float over a batch of 8 rows folded into a double), stored to dslope when
+ * the group ends; the part of a group that continues in a neighbouring chunk goes to a workspace
+ * slab [S][2 ends][chunks][K] that a finishing launch adds in chunk order in fp64 (it also writes
+ * the zeros of the empty groups). No floating-point atomics: two calls on the same inputs give the
+ * same bits. The workspace is mi_gather_linear's (with P as given) plus that slab.
+ * MI_EINVAL: those of mi_gather_site, and a role[0] that is not a GATHER role, S < 1, a NULL table
+ * or z among the first S slopes, P < 0, P >= 1 with a NULL x or theta. MI_EUNSUPPORTED: those of
+ * mi_gather_site, S > MI_GATHER_MAX_SLOPES and P > MI_GATHER_LINEAR_MAX_P (from
+ * mi_gather_slopes_workspace_bytes too). MI_EWORKSPACE: a workspace smaller than
+ * mi_gather_slopes_workspace_bytes asks for. All checked before any device work. */
+#define MI_GATHER_MAX_SLOPES 4
+typedef struct mi_gather_slope {
+  const float* table;     /* beta_s[k, g] at table[k * stride_k + g * stride_g] */
+  int64_t stride_k;
+  int64_t stride_g;
+  const float* z;         /* z_s[i] at z[i * z_stride_i] */
+  int64_t z_stride_i;
+} mi_gather_slope;
+
+typedef struct mi_gather_slopes {
+  mi_gather_linear linear;   /* site.role[0] must be a GATHER role; P may be 0 */
+  int64_t S;
+  mi_gather_slope slope[MI_GATHER_MAX_SLOPES];
+} mi_gather_slopes;
+
+int mi_gather_slopes_struct_size(size_t* bytes);
+int mi_gather_slopes_workspace_bytes(const mi_gather_slopes* site, size_t* bytes);
+int mi_gather_slopes_forward(const mi_gather_slopes* site, void* workspace, size_t workspace_bytes,
+                             float* total /* [K] */, const mi_gather_grads* grads /* or NULL */,
+                             float* dtheta /* [K, P] contiguous or NULL */,
+                             float* const dslope[MI_GATHER_MAX_SLOPES] /* or NULL */,
+                             uint32_t* flags, void* stream);
+
 /* ---- device-resident minibatches (replaces examples/minibatch.md:78-88, the host DataLoader) ---- */
 
 /* Row indices of the next minibatch of an n-row dataset: with c = counter[0] (then counter[0] =

@@ -210,6 +210,26 @@ class GatherLinear(ctypes.Structure):
     ]
 
 
+GATHER_MAX_SLOPES = 4   # MI_GATHER_MAX_SLOPES
+
+
+class GatherSlope(ctypes.Structure):
+    """mi_gather_slope (include/mininf_amd.h)."""
+    _fields_ = [
+        ("table", c_vp), ("stride_k", c_i64), ("stride_g", c_i64),
+        ("z", c_vp), ("z_stride_i", c_i64),
+    ]
+
+
+class GatherSlopes(ctypes.Structure):
+    """mi_gather_slopes (include/mininf_amd.h)."""
+    _fields_ = [
+        ("linear", GatherLinear),
+        ("S", c_i64),
+        ("slope", GatherSlope * GATHER_MAX_SLOPES),
+    ]
+
+
 class Source(ctypes.Structure):
     _fields_ = [("ptr", c_vp), ("stride_k", c_i64), ("stride_i", c_i64)]
 
@@ -469,6 +489,12 @@ _SIGNATURES = {
     "mi_gather_linear_forward": (ctypes.c_int, [ctypes.POINTER(GatherLinear), c_vp, ctypes.c_size_t,
                                                 c_vp, ctypes.POINTER(GatherGrads), c_vp, c_vp,
                                                 c_vp]),
+    "mi_gather_slopes_struct_size": (ctypes.c_int, [ctypes.POINTER(ctypes.c_size_t)]),
+    "mi_gather_slopes_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(GatherSlopes),
+                                                        ctypes.POINTER(ctypes.c_size_t)]),
+    "mi_gather_slopes_forward": (ctypes.c_int, [ctypes.POINTER(GatherSlopes), c_vp, ctypes.c_size_t,
+                                                c_vp, ctypes.POINTER(GatherGrads), c_vp,
+                                                ctypes.POINTER(c_vp), c_vp, c_vp]),
     "mi_minibatch_rows": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, ctypes.c_int32,
                                          ctypes.c_uint64, c_vp, c_i64, c_vp]),
     "mi_gather_rows": (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
@@ -550,6 +576,12 @@ def lib() -> ctypes.CDLL:
         if gather_linear.value != ctypes.sizeof(GatherLinear):
             raise NativeError(f"{LIB_PATH} lays mi_gather_linear out in {gather_linear.value} bytes, "
                               f"this binding in {ctypes.sizeof(GatherLinear)}; rebuild it "
+                              "(mininf_amd/build.py --force).")
+        gather_slopes = ctypes.c_size_t()
+        handle.mi_gather_slopes_struct_size(ctypes.byref(gather_slopes))
+        if gather_slopes.value != ctypes.sizeof(GatherSlopes):
+            raise NativeError(f"{LIB_PATH} lays mi_gather_slopes out in {gather_slopes.value} bytes, "
+                              f"this binding in {ctypes.sizeof(GatherSlopes)}; rebuild it "
                               "(mininf_amd/build.py --force).")
         _LIB = handle
     return _LIB

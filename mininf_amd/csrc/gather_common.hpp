@@ -1,5 +1,5 @@
 // What the group-indexed site kernels share (gather_site.hip: mi_gather_site, gather_linear_site.hip:
-// mi_gather_linear): the lane's accumulators, what a (group, particle) fixes of a density, the
+// mi_gather_linear, gather_slopes_site.hip: mi_gather_slopes): the lane's accumulators, what a (group, particle) fixes of a density, the
 // launch's workspace layout and the finishing launches (k_gather_sums, k_gather_tables, defined in
 // gather_site.hip and launched through gs_finish).
 #pragma once
@@ -107,6 +107,25 @@ struct GsTerms {
     else return !(v >= 0.0f && v == floorf(v));
   }
 };
+
+// [lo, hi): the sorted rows of group g (two binary searches of sorted_group [N]).
+__device__ __forceinline__ void gs_group_rows(const int32_t* __restrict__ sg, int64_t N, int64_t g,
+                                              int64_t& lo, int64_t& hi) {
+  int64_t a = 0, b = N;
+  while (a < b) {
+    const int64_t m = (a + b) >> 1;
+    if ((int64_t)sg[m] < g) a = m + 1;
+    else b = m;
+  }
+  lo = a;
+  b = N;
+  while (a < b) {
+    const int64_t m = (a + b) >> 1;
+    if ((int64_t)sg[m] <= g) a = m + 1;
+    else b = m;
+  }
+  hi = a;
+}
 
 // ---- host side ------------------------------------------------------------------------------------
 
@@ -217,5 +236,10 @@ inline int gs_bind(const mi_gather_site* site, const GsLayout& y, void* workspac
 // dtable entries the site kernel did not store itself. 0 or an MI_* code.
 int gs_finish(const mi_gather_site* site, const GsWork& W, double gscale, const int table_roles[2],
               int ntables, hipStream_t s);
+
+// The launch that finishes dtheta (gather_linear_site.hip, k_gather_dtheta): dtheta[k, j] =
+// gscale * the sum over the chunks of dth[j][chunk][k], in chunk order. 0 or an MI_* code.
+int gl_dtheta(const float* dth, int64_t nchunk, int64_t K, int P, double gscale, float* dtheta,
+              hipStream_t s);
 
 }  // namespace mi

@@ -288,6 +288,15 @@ __global__ __launch_bounds__(32 * kGlParts) void k_gather_dtheta(const float* __
   }
 }
 
+// (gather_common.hpp)
+int gl_dtheta(const float* dth, int64_t nchunk, int64_t K, int P, double gscale, float* dtheta,
+              hipStream_t s) {
+  hipLaunchKernelGGL(k_gather_dtheta, dim3((unsigned)ceil_div(K, 32), (unsigned)P),
+                     dim3(32 * kGlParts), 0, s, dth, nchunk, K, P, gscale, dtheta);
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? to_code(e) : 0;
+}
+
 }  // namespace mi
 
 namespace {
@@ -362,12 +371,7 @@ int mi_gather_linear_forward(const mi_gather_linear* site, void* workspace, size
   if ((e = hipGetLastError()) != hipSuccess) return to_code(e);
   const int code = mi::gs_finish(base, W, gscale, table_roles, ntables, s);
   if (code != 0) return code;
-  if (dtheta != nullptr) {
-    hipLaunchKernelGGL(mi::k_gather_dtheta, dim3((unsigned)ceil_div(base->K, 32), (unsigned)site->P),
-                       dim3(32 * mi::kGlParts), 0, s, dth, y.nchunk, base->K, (int)site->P, gscale,
-                       dtheta);
-    if ((e = hipGetLastError()) != hipSuccess) return to_code(e);
-  }
+  if (dtheta != nullptr) return mi::gl_dtheta(dth, y.nchunk, base->K, (int)site->P, gscale, dtheta, s);
   return 0;
 }
 

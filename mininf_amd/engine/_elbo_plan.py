@@ -433,7 +433,8 @@ class _ElboPlan:
         loss after this plan ran); gathered_sites: sites on the model's own ``alpha[group]`` that
         this evaluation ran on a gather kernel (no [K, N] gather, no scatter-add);
         gathered_linear_sites: those of them with fixed effects, ``alpha[group] + X @ theta``, on
-        mi_gather_linear_forward (no [K, N] product either).
+        mi_gather_linear_forward (no [K, N] product either); gathered_slope_sites: those of the
+        gathered sites with slope terms ``beta[group] * z``, on mi_gather_slopes_forward.
         """
         return {
             "folded_priors": sum(l.prior is not None for l in self.launchers) +
@@ -456,6 +457,9 @@ class _ElboPlan:
             "gathered_linear_sites": sum(site.gather is not None and site.gather.linear and
                                          site.gather.launches > 0
                                          for site, _, _, _ in self.categorical),
+            "gathered_slope_sites": sum(site.gather is not None and site.gather.slopes and
+                                        site.gather.launches > 0
+                                        for site, _, _, _ in self.categorical),
         }
 
     def _reduce_ok(self, assume=None) -> bool:

@@ -3,7 +3,8 @@ Group-indexed sites: Normal / Bernoulli-logits / Poisson sites whose parameter i
 gather ``alpha[group]`` of a per-particle table [K, G], fused (``mi_gather_site_forward``; the
 gather was deferred by :mod:`mininf_amd.linear`), and those whose first role also has fixed
 effects, ``alpha[group] + X @ theta`` (``mi_gather_linear_forward``: theta [K, P] joins the
-launcher's parameters). Such a site is planned as a row site -- an entry
+launcher's parameters) or varying slopes, ``alpha[group] + beta[group] * z [+ X @ theta]``
+(``mi_gather_slopes_forward``: the slope tables [K, G] join the parameters too). Such a site is planned as a row site -- an entry
 (site, parameters, value, mask) of the planner's categorical list whose record carries its launcher
 (``site.gather``) -- so the ELBO plan, ``log_joint`` and ``LogLikelihoodLoss`` take it like any row
 site: its speculative gradients are dense in every parameter (the tables [K, G], per-particle
@@ -88,10 +89,14 @@ class _Role:
         # role 0's linear term: the observed X [N, P] and theta's position among the parameters
         self.X: Optional[torch.Tensor] = None
         self.theta_param = -1
+        # role 0's slope terms: the observed columns [N] and the tables' positions
+        self.slope_z: List[torch.Tensor] = []
+        self.slope_params: List[int] = []
 
 
 class _GatherLauncher:
-    """One ``mi_gather_site_forward`` site."""
+    """One ``mi_gather_site_forward`` / ``mi_gather_linear_forward`` / ``mi_gather_slopes_forward``
+    site."""
     def __init__(self, site: SiteRecord, K: int, device: torch.device, roles: List[_Role],
                  order: torch.Tensor, sorted_group: torch.Tensor, G: int, value: torch.Tensor,
                  mask: Optional[torch.Tensor]) -> None:
@@ -102,7 +107,24 @@ class _GatherLauncher:
         self.value = value            # [N] float32 or int64
         self.mask = mask              # [N] bool or None
         self.launches = 0             # kernel calls that ran (not declined)
-        self.linear = roles[0].X is not None   # mi_gather_linear_forward
+        self.linear = roles[0].X is not None   # an X @ theta term (mi_gather_linear_forward)
+        self.slopes = bool(roles[0].slope_params)   # mi_gather_slopes_forward
+
+    def describe_slopes(self, params: Tuple[torch.Tensor, ...], g0: float) -> nat.GatherSlopes:
+        M = nat.GatherSlopes()
+        if self.linear:
+            M.linear = self.describe_linear(params, g0)
+        else:
+            M.linear.site = self.describe(params, g0)
+        role = self.roles[0]
+        M.S = len(role.slope_params)
+        for s, (where, z) in enumerate(zip(role.slope_params, role.slope_z)):
+            table = params[where]
+            M.slope[s].table = table.data_ptr()
+            M.slope[s].stride_k, M.slope[s].stride_g = table.stride()
+            M.slope[s].z = z.data_ptr()
+            M.slope[s].z_stride_i = z.stride(0)
+        return M
 
     def describe_linear(self, params: Tuple[torch.Tensor, ...], g0: float) -> nat.GatherLinear:
         M = nat.GatherLinear()
@@ -164,9 +186,12 @@ class _GatherLauncher:
         """(total [K], the speculative gradients of ``params`` -- None where none is needed --,
         flags [1])."""
         device = self.device
-        L = self.describe_linear(params, g0) if self.linear else self.describe(params, g0)
+        L = self.describe_slopes(params, g0) if self.slopes else \
+            self.describe_linear(params, g0) if self.linear else self.describe(params, g0)
         if flags is None:
             flags = torch.empty(1, dtype=torch.int32, device=device)
+        elif self.slopes:
+            L.linear.site.options |= nat.GROUP_FLAGS_ZEROED
         elif self.linear:
             L.site.options |= nat.GROUP_FLAGS_ZEROED
         else:
@@ -184,13 +209,29 @@ class _GatherLauncher:
         size = ctypes.c_size_t()
         lib = nat.lib()
         total = torch.empty(self.K, dtype=torch.float32, device=device)
+        dtheta = None
         if self.linear:
             where = self.roles[0].theta_param
-            dtheta = None
             if params[where].requires_grad:   # [K, P] contiguous, every entry written
                 grads[where] = torch.empty(tuple(params[where].shape), dtype=torch.float32,
                                            device=device)
                 dtheta = grads[where].data_ptr()
+        if self.slopes:
+            dslope = (nat.c_vp * nat.GATHER_MAX_SLOPES)()
+            for s, where in enumerate(self.roles[0].slope_params):
+                if params[where].requires_grad:   # [K, G] contiguous, every entry written
+                    grads[where] = torch.empty(tuple(params[where].shape), dtype=torch.float32,
+                                               device=device)
+                    dslope[s] = grads[where].data_ptr()
+            code = lib.mi_gather_slopes_workspace_bytes(ctypes.byref(L), ctypes.byref(size))
+            if code == nat.MI_EUNSUPPORTED:
+                return self._materialised(params, g0, flags)
+            nat.check(code, "mi_gather_slopes_workspace_bytes")
+            workspace = torch.empty(max(1, size.value), dtype=torch.uint8, device=device)
+            code = lib.mi_gather_slopes_forward(ctypes.byref(L), workspace.data_ptr(), size.value,
+                                                total.data_ptr(), ctypes.byref(G), dtheta, dslope,
+                                                flags.data_ptr(), nat.stream_handle(device))
+        elif self.linear:
             code = lib.mi_gather_linear_workspace_bytes(ctypes.byref(L), ctypes.byref(size))
             if code == nat.MI_EUNSUPPORTED:
                 return self._materialised(params, g0, flags)
@@ -208,7 +249,8 @@ class _GatherLauncher:
                                               nat.stream_handle(device))
         if code == nat.MI_EUNSUPPORTED:
             return self._materialised(params, g0, flags)
-        nat.check(code, "mi_gather_linear_forward" if self.linear else "mi_gather_site_forward")
+        nat.check(code, "mi_gather_slopes_forward" if self.slopes else
+                  "mi_gather_linear_forward" if self.linear else "mi_gather_site_forward")
         self.launches += 1
         return total, tuple(grads), flags
 
@@ -225,6 +267,9 @@ class _GatherLauncher:
         index = torch.empty(self.N, dtype=torch.int64, device=self.device)
         index[self.order.long()] = self.sorted_group.long()
         linear = params[role.theta_param] @ role.X.t() if role.X is not None else None
+        for where, z in zip(role.slope_params, role.slope_z):
+            term = params[where][:, index] * z
+            linear = term if linear is None else linear + term
         return _affine(tensor[:, index], params[role.shift_param] if role.shift_param >= 0
                        else role.shift, params[role.mult_param] if role.mult_param >= 0
                        else role.mult, role.link == nat.GATHER_LINK_EXP, linear)
@@ -254,8 +299,8 @@ class _GatherLauncher:
 
 
 def _affine(gathered: torch.Tensor, shift, mult, exp: bool, linear=None) -> torch.Tensor:
-    """link(shift + mult * gathered [+ linear]) for [K, N] ``gathered`` (and ``linear``) and None /
-    number / [K] terms."""
+    """link(shift + mult * gathered [+ linear]) for [K, N] ``gathered`` (and ``linear``, the slope
+    terms and the fixed effects together) and None / number / [K] terms."""
     K = gathered.shape[0]
     if mult is not None:
         gathered = (mult.reshape(K, 1) if isinstance(mult, torch.Tensor) else mult) * gathered
@@ -315,8 +360,18 @@ def plan_gather(site: SiteRecord, K: int, device: torch.device):
                 1 <= X.shape[1] <= nat.GATHER_LINEAR_MAX_P and data.lookup(X) is None and \
                 theta.dtype == torch.float32 and theta.device == device and \
                 tuple(theta.shape) == (K, X.shape[1])
+        if g.slope_tables:
+            # slope terms: float32 tables [K, G'] (G' = G is checked below) and float32 columns
+            # [N] on the device, held whole (not a DeviceDataLoader column)
+            ok = ok and g is site.gather_roles[0] and len(live) == 1 and \
+                len(g.slope_tables) <= nat.GATHER_MAX_SLOPES and all(
+                    t.dtype == torch.float32 and t.dim() == 2 and t.device == device and
+                    t.shape[0] == K and
+                    z.dtype == torch.float32 and z.device == device and not z.requires_grad and
+                    z.dim() == 1 and z.shape[0] == N and data.lookup(z) is None
+                    for t, z in zip(g.slope_tables, g.slope_z))
     G = int(live[0].table.shape[1]) if ok else 0
-    ok = ok and all(int(g.table.shape[1]) == G for g in live)
+    ok = ok and all(int(t.shape[1]) == G for g in live for t in [g.table, *g.slope_tables])
     ok_index = ok
     plan = index_plan(index, G) if ok else None
     roles: List[_Role] = []
@@ -345,6 +400,10 @@ def plan_gather(site: SiteRecord, K: int, device: torch.device):
                 role.X = g.linear_X
                 role.theta_param = len(params)
                 params.append(g.linear_theta)
+            for table, z in zip(g.slope_tables, g.slope_z):
+                role.slope_params.append(len(params))
+                params.append(table)
+                role.slope_z.append(z)
             roles.append(role)
             continue
         t, constant = _to_device(site.tensors[r], K, device, f"site '{site.name}'")

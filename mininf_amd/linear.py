@@ -27,6 +27,8 @@ broadcasting views                    either  any                    unchanged
 ``exp(ph)``                           either  identity               exp
 ``ph + c``, ``ph - c``, ``ph * c``    gather  identity               identity
 ``gather + matmul`` (``defer_sum``)   both    identity, identity     identity
+``gather * z`` (``defer_slope``)      gather  identity (root)        (a product)
+``gather + product``                  gather  identity               identity
 ``ph.logsumexp(-1, keepdim=True)``    matmul  identity, log_softmax  logsumexp
 ``log_softmax(ph, -1)``               matmul  identity, log_softmax  log_softmax
 ``ph - lse``                          matmul  identity, log_softmax  log_softmax
@@ -43,6 +45,15 @@ affine chain and the root placeholder of ``X @ theta`` for a vector ``theta`` of
 ``theta`` and which operand stood on the left (``mi_gather_linear_forward``). It still takes
 ``+ c``, ``- c`` (composed into ``shift``, remembered in ``post``) and ``exp``; ``* c`` and ``c - ...``
 (which would negate the linear term) materialise, like a second gather or product.
+With ``defer_slope`` the product (``mul`` in all its forms, either order) of a root gather
+placeholder ``beta[index]`` and an observed float32 column ``z`` [N] is a *product* placeholder
+(kind ``"slope"``) whose only accepted use is as a summand: the sum (``add``, either order) of an
+identity-link gather record -- any affine chain, with or without the ``X @ theta`` above, holding
+fewer than ``MAX_SLOPES`` slopes -- and a product whose gather used the same index tensor object is
+a gather-kind record with one more slope (``mi_gather_slopes_forward``). A record that holds slopes
+still takes ``X @ theta`` once, ``+ c``, ``- c`` and ``exp``; ``summands`` remembers every operation
+after the gather's own chain in the model's order and sides. Any other call on a product first
+makes ``table[index] * z`` real, in the order the model wrote it.
 Metadata queries and ``x.type_as(ph)`` read no values and pass a placeholder through.
 
 **Anything else materialises.** Every other torch operation that meets a placeholder first gets its
@@ -103,6 +114,8 @@ _ARITHMETIC = {"add": _ADDS, "sub": _SUBS, "mul": _MULS}
 MAX_CATEGORIES = 32
 # Most columns of X in a deferred ``alpha[group] + X @ theta`` (MI_GATHER_LINEAR_MAX_P).
 MAX_SUM_FEATURES = 32
+# Most slope terms ``beta[group] * z`` of one deferred predictor (MI_GATHER_MAX_SLOPES).
+MAX_SLOPES = 4
 
 
 class NeedsDraws(Exception):
@@ -154,7 +167,13 @@ class Deferred:
     order, for :func:`put_back`: ("add" | "sub" | "mul", c, left), the placeholder the left
     operand or not. After a deferred sum ``X`` and ``theta`` are the product's, ``linear_left``
     says whether the gather was the sum's left operand and ``post`` lists the later scalar
-    operations like ``chain``.
+    operations like ``chain``. ``slopes`` lists the slope terms of the predictor, (table, z, whether
+    the table was the product's left operand), and ``summands`` every operation after ``chain`` in
+    the model's order: ("slope", position in ``slopes``, left), ("linear", None, left) or a scalar
+    operation like those of ``chain``, ``left`` saying whether the record was the left operand.
+
+    ``"slope"``: the product ``table[index] * z`` of a root gather placeholder (``parent``) and an
+    observed column ``z``; ``slope_left`` says whether the gather was the product's left operand.
     """
     kind: str
     shape: torch.Size
@@ -172,6 +191,10 @@ class Deferred:
     chain: Tuple[Tuple[str, Any, bool], ...] = ()
     linear_left: bool = True
     post: Tuple[Tuple[str, Any, bool], ...] = ()
+    slopes: Tuple[Tuple[torch.Tensor, torch.Tensor, bool], ...] = ()
+    summands: Tuple[Tuple[str, Any, bool], ...] = ()
+    z: Optional[torch.Tensor] = None
+    slope_left: bool = True
 
     @property
     def root(self) -> "Deferred":
@@ -210,7 +233,8 @@ class DeferredMatmul(TorchFunctionMode):
     require_device = True   # defer only device operands (the fused kernels')
 
     def __init__(self, K: int, defer_matmul: bool = True,
-                 defer_gather: Optional[bool] = None, defer_sum: bool = False) -> None:
+                 defer_gather: Optional[bool] = None, defer_sum: bool = False,
+                 defer_slope: bool = False) -> None:
         super().__init__()
         self.K = K
         self.defer_matmul = defer_matmul
@@ -218,6 +242,8 @@ class DeferredMatmul(TorchFunctionMode):
             else defer_gather
         # (the sum of both predictors needs both deferred)
         self.defer_sum = bool(defer_sum and self.defer_matmul and self.defer_gather)
+        # (a slope is a summand beside a deferred gather)
+        self.defer_slope = bool(defer_slope and self.defer_gather)
         self.deferred: Dict[int, Deferred] = {}   # id(placeholder) -> its record
         # per-particle scalars broadcast beside a gather placeholder (Normal's broadcast_all of
         # loc and scale): the broadcast view -> the scalar it came from
@@ -356,7 +382,7 @@ class DeferredMatmul(TorchFunctionMode):
         if func not in _EXPS or len(args) != 1 or kwargs:
             return None
         info = self._accepted(args[0], None, ("identity",))
-        if info is None:
+        if info is None or info.kind == "slope":
             return None
         if info.kind == "matmul":
             return _matmul_derived(info.root, info.shape, "exp")
@@ -379,7 +405,7 @@ class DeferredMatmul(TorchFunctionMode):
         info = self._accepted(ph, "gather", ("identity",))
         if info is None:
             return None
-        summed = info.X is not None
+        summed = info.X is not None or bool(info.slopes)
         if summed and (op == "mul" or (op == "sub" and not left)):
             return None   # (the kernel's linear term has no factor of its own)
         shift, mult = info.shift, info.mult
@@ -400,7 +426,8 @@ class DeferredMatmul(TorchFunctionMode):
             return func(*(operands[::-1] if reflected else operands))
         if summed:
             return info.derived(shift=shift, mult=mult, replay=replay,
-                                post=info.post + ((op, c, left),))
+                                post=info.post + ((op, c, left),),
+                                summands=info.summands + ((op, c, left),))
         return info.derived(shift=shift, mult=mult, replay=replay,
                             chain=info.chain + ((op, c, left),))
 
@@ -408,13 +435,15 @@ class DeferredMatmul(TorchFunctionMode):
         """``gather + matmul`` in either order (``defer_sum``): an identity-link gather placeholder
         with any affine chain and the identity-link root of ``X @ theta`` for a vector ``theta``,
         both over the same N."""
-        if not self.defer_sum or func not in _ADDS or kwargs or len(args) != 2:
+        if func not in _ADDS or kwargs or len(args) != 2:
             return None
         x, y = (args[1], args[0]) if _ADDS[func] else args   # the call computes x + y
         left = self.lookup(x, "gather") is not None
         g = self._accepted(x if left else y, "gather", ("identity",))
+        if g is not None and self.lookup(y if left else x, "slope") is not None:
+            return self._sum_slope(func, g, self.lookup(y if left else x, "slope"), left)
         m = self._accepted(y if left else x, "matmul", ("identity",))
-        if g is None or m is None or g.X is not None or m.parent is not None or \
+        if not self.defer_sum or g is None or m is None or g.X is not None or m.parent is not None or \
                 m.theta.dim() != 1 or m.theta.shape[0] > MAX_SUM_FEATURES or \
                 tuple(g.shape) != tuple(m.shape) or len(g.shape) != 1 or \
                 m.X.device != g.table.device:
@@ -425,7 +454,46 @@ class DeferredMatmul(TorchFunctionMode):
             with self._bypassed():
                 operands = (real, product) if left else (product, real)
                 return func(*(operands[::-1] if _ADDS[func] else operands))
-        return g.derived(X=m.X, theta=m.theta, linear_left=left, replay=replay)
+        return g.derived(X=m.X, theta=m.theta, linear_left=left, replay=replay,
+                         summands=g.summands + (("linear", None, left),))
+
+    def _slope(self, func: Callable, args, kwargs) -> Optional[Deferred]:
+        """``gather * z`` in either order (``defer_slope``): a root gather placeholder (identity
+        link, no chain, no ``X``, no slopes) and an observed float32 column ``z`` of its length on
+        the table's device: a product placeholder."""
+        if not self.defer_slope or func not in _MULS or kwargs or len(args) != 2:
+            return None
+        x, y = (args[1], args[0]) if _MULS[func] else args   # the call computes x * y
+        left = self.lookup(x, "gather") is not None
+        g = self._accepted(x if left else y, "gather", ("identity",))
+        z = y if left else x
+        if g is None or g.parent is not None or not isinstance(z, torch.Tensor) or \
+                self.lookup(z) is not None or lazy_of(z) is not None or \
+                _functorch.is_batchedtensor(z) or z.dtype != torch.float32 or z.dim() != 1 or \
+                tuple(z.shape) != tuple(g.shape) or z.device != g.table.device or z.requires_grad:
+            return None
+
+        def replay(real):
+            operands = (real, z) if left else (z, real)
+            return func(*(operands[::-1] if _MULS[func] else operands))
+        new = g.derived(replay=replay, z=z, slope_left=left)
+        new.kind = "slope"
+        return new
+
+    def _sum_slope(self, func: Callable, g: Deferred, p: Deferred, left: bool) -> Optional[Deferred]:
+        """``gather + product`` (the gather record the left operand or not): one more slope."""
+        if p.parent is None or p.parent.kind != "gather" or p.index is not g.index or \
+                len(g.slopes) >= MAX_SLOPES or tuple(g.shape) != tuple(p.shape) or \
+                len(g.shape) != 1 or p.table.device != g.table.device:
+            return None
+
+        def replay(real):
+            product = self._real(p)
+            with self._bypassed():
+                operands = (real, product) if left else (product, real)
+                return func(*(operands[::-1] if _ADDS[func] else operands))
+        return g.derived(slopes=g.slopes + ((p.table, p.z, p.slope_left),), replay=replay,
+                         summands=g.summands + (("slope", len(g.slopes), left),))
 
     def _softmax_operand(self, args) -> Optional[Deferred]:
         """The record of ``args[0]`` if a softmax normalisation may derive from it: a [.., N, C]
@@ -461,7 +529,7 @@ class DeferredMatmul(TorchFunctionMode):
         return _matmul_derived(info.root, info.shape, "log_softmax", info.steps + ("sub",))
 
     # tried in this order; a call none of them accepts materialises its placeholders
-    _DERIVATIONS = (_exp, _affine, _sum, _logsumexp, _log_softmax, _sub_logsumexp)
+    _DERIVATIONS = (_exp, _affine, _slope, _sum, _logsumexp, _log_softmax, _sub_logsumexp)
 
     # ---- the mode ----------------------------------------------------------------------------
     def __torch_function__(self, func: Callable, types, args=(), kwargs=None):
@@ -531,6 +599,25 @@ class DeferredMatmul(TorchFunctionMode):
         return func(*args, **kwargs)
 
 
+def _summands_back(g, real: torch.Tensor, K: int) -> torch.Tensor:
+    """The operations after the gather's chain of a role that holds slopes, in the model's order
+    and on its sides: the slope products ``table[:, index] * z``, the product ``X @ theta`` as
+    put_back spells a vector regression, the scalar terms."""
+    for kind, c, left in g.summands:
+        if kind == "slope":
+            gathered = g.slope_tables[c][:, g.index]
+            term = gathered * g.slope_z[c] if g.slope_left[c] else g.slope_z[c] * gathered
+        elif kind == "linear":
+            term = g.linear_theta @ g.linear_X.t()
+        else:
+            term = c.reshape(K, 1) if isinstance(c, torch.Tensor) else c
+        if kind == "sub":
+            real = real - term
+        else:
+            real = real + term if left else term + real
+    return real
+
+
 def put_back(site, K: int) -> None:
     """
     Restore what the model wrote where a planner's kernel cannot take a site recorded on a deferred
@@ -553,7 +640,9 @@ def put_back(site, K: int) -> None:
                     real = real - c if left else c - real
                 else:
                     real = real * c if left else c * real
-            if g.linear_X is not None:
+            if g.slope_tables:
+                real = _summands_back(g, real, K)
+            elif g.linear_X is not None:
                 # the product as put_back spells a vector regression, the sum in the model's
                 # operand order, then the later scalar operations
                 product = g.linear_theta @ g.linear_X.t()

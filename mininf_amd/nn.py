@@ -615,21 +615,24 @@ class EvidenceLowerBoundLoss(nn.Module):
                                      element_offsets=offsets)
             try:
                 trace = particles.trace_particles(model, samples, K, validate=self.validate,
-                                                  defer_sum=switches.enabled("DEFER_SUM"))
+                                                  defer_sum=switches.enabled("DEFER_SUM"),
+                                                  defer_slope=switches.enabled("DEFER_SLOPE"))
             except linear.NeedsDraws:
                 guide.release_lazy()
                 samples = guide.draw_all(approximation, K, self.seed, 0, offset, _noise,
                                          step_device=step, step_snapshot=snapshot,
                                          element_offsets=offsets)
                 trace = particles.trace_particles(model, samples, K, validate=self.validate,
-                                                  defer_sum=switches.enabled("DEFER_SUM"))
+                                                  defer_sum=switches.enabled("DEFER_SUM"),
+                                                  defer_slope=switches.enabled("DEFER_SLOPE"))
         else:
             samples = approximation.rsample(torch.Size([K]))
             if not isinstance(samples, Dict):
                 raise TypeError("Expected a distribution which samples dictionaries of tensors "
                                 f"but got a sample of type {type(samples)}")
             trace = particles.trace_particles(model, samples, K, validate=self.validate,
-                                                  defer_sum=switches.enabled("DEFER_SUM"))
+                                                  defer_sum=switches.enabled("DEFER_SUM"),
+                                                  defer_slope=switches.enabled("DEFER_SLOPE"))
         # d loss / d T_k = -1 / K exactly (fp32), matching the `mul(-1/K)` below.
         g0 = _float32(-1.0 / self.num_particles)
         device = next((t.device for t in samples.values() if isinstance(t, torch.Tensor)),
@@ -749,7 +752,8 @@ class LogLikelihoodLoss(nn.Module):
         if observed:
             model = condition(model, **observed)
         trace = particles.trace_particles(model, samples, 1,
-                                          defer_sum=switches.enabled("DEFER_SUM"))
+                                          defer_sum=switches.enabled("DEFER_SUM"),
+                                          defer_slope=switches.enabled("DEFER_SLOPE"))
         joint = engine.log_joint(trace, -1.0, device)
         collector = graph.deferred()
         if collector is not None:

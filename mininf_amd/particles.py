@@ -150,6 +150,15 @@ class GatherRole:
     linear_theta: Optional[torch.Tensor] = None
     linear_left: bool = True
     post: List[Tuple[str, Any, bool]] = dataclasses.field(default_factory=list)
+    # varying slopes, + sum_s slope_tables[s][:, index] * slope_z[s]: per slope the table (an output
+    # index; after tracing [K, G]), the observed column [N] and whether the table was the product's
+    # left operand; ``summands`` lists every operation after ``chain`` in the model's order,
+    # ("slope", s, left) | ("linear", None, left) | a scalar operation like those of ``chain``
+    slope_outputs: List[int] = dataclasses.field(default_factory=list)
+    slope_tables: List[torch.Tensor] = dataclasses.field(default_factory=list)
+    slope_z: List[torch.Tensor] = dataclasses.field(default_factory=list)
+    slope_left: List[bool] = dataclasses.field(default_factory=list)
+    summands: List[Tuple[str, Any, bool]] = dataclasses.field(default_factory=list)
 
 
 @dataclasses.dataclass
@@ -625,7 +634,12 @@ class ParticleTracer(TracerMixin):
                 linear_X=g.X, linear_theta_output=self._emit(g.theta) if g.X is not None else -1,
                 linear_left=g.linear_left,
                 post=[(op, ("output", self._emit(c)) if isinstance(c, torch.Tensor) else c, left)
-                      for op, c, left in g.post]) for g in gathered]
+                      for op, c, left in g.post],
+                slope_outputs=[self._emit(table) for table, _, _ in g.slopes],
+                slope_z=[z for _, z, _ in g.slopes],
+                slope_left=[table_left for _, _, table_left in g.slopes],
+                summands=[(op, ("output", self._emit(c)) if isinstance(c, torch.Tensor) else c, left)
+                          for op, c, left in g.summands]) for g in gathered]
         self.sites.append(record)
         return value
 
@@ -704,7 +718,8 @@ class ParticleTracer(TracerMixin):
             return None
         # a deferred sum is role 0 and the site's only gathered role (a gathered scale beside
         # it materialises)
-        if any(info.X is not None for info in live) and (len(live) > 1 or infos[0] is None):
+        if any(info.X is not None or info.slopes for info in live) and \
+                (len(live) > 1 or infos[0] is None):
             return None
         return infos
 
@@ -835,7 +850,8 @@ _NO_VALIDATE = object()
 
 def trace_particles(model: Callable, samples: Dict[str, torch.Tensor], K: int,
                     validate: bool = True, defer_matmul: Optional[bool] = None,
-                    lift_host: bool = False, defer_sum: bool = False) -> ParticleTrace:
+                    lift_host: bool = False, defer_sum: bool = False,
+                    defer_slope: bool = False) -> ParticleTrace:
     """
     Run ``condition(model, **samples)`` once under ``vmap`` over the leading (particle) dimension of
     every sample and return the recorded sites with [K, ...] tensors. With ``defer_matmul``,
@@ -843,22 +859,26 @@ def trace_particles(model: Callable, samples: Dict[str, torch.Tensor], K: int,
     kernels instead of by the model (:mod:`mininf_amd.linear`). A model that mixes its own host
     tensors with the device particles, or factorises a matrix, is traced again under
     :class:`TraceCompat`. With ``defer_sum`` (and both deferrals on) the sum
-    ``alpha[group] + X @ theta`` is recorded as one gathered site with a linear term.
+    ``alpha[group] + X @ theta`` is recorded as one gathered site with a linear term; with
+    ``defer_slope`` (and the gather deferral on) slope terms ``beta[group] * z`` added to a gathered
+    predictor are recorded with it.
     """
     device = next((t.device for t in samples.values() if isinstance(t, torch.Tensor)), None)
     lift = device if device is not None and device.type != "cpu" else None
     if not lift_host:
         try:
-            return _trace(model, samples, K, validate, defer_matmul, False, None, defer_sum)
+            return _trace(model, samples, K, validate, defer_matmul, False, None, defer_sum,
+                          defer_slope)
         except RuntimeError as error:
             if not _needs_compat(error):
                 raise
-    return _trace(model, samples, K, validate, defer_matmul, True, lift, defer_sum)
+    return _trace(model, samples, K, validate, defer_matmul, True, lift, defer_sum, defer_slope)
 
 
 def _trace(model: Callable, samples: Dict[str, torch.Tensor], K: int, validate: bool,
            defer_matmul: Optional[bool], compat: bool,
-           lift: Optional[torch.device], defer_sum: bool = False) -> ParticleTrace:
+           lift: Optional[torch.device], defer_sum: bool = False,
+           defer_slope: bool = False) -> ParticleTrace:
     from .linear import DeferredMatmul
 
     if defer_matmul is None:
@@ -873,7 +893,8 @@ def _trace(model: Callable, samples: Dict[str, torch.Tensor], K: int, validate: 
         flush_draws()   # no mode watches the model's reads of deferred guide draws
 
     def per_particle(*values):
-        mode = DeferredMatmul(K, defer_matmul, defer_gather, defer_sum) if use_mode else None
+        mode = DeferredMatmul(K, defer_matmul, defer_gather, defer_sum, defer_slope) \
+            if use_mode else None
         tracer.deferred = mode
         with tracer, contextlib.ExitStack() as stack:
             if lift is not None:
@@ -917,6 +938,9 @@ def _trace(model: Callable, samples: Dict[str, torch.Tensor], K: int, validate: 
                     g.linear_theta = outputs[g.linear_theta_output]
                 g.post = [(op, outputs[c[1]] if isinstance(c, tuple) else c, left)
                           for op, c, left in g.post]
+                g.slope_tables = [outputs[index] for index in g.slope_outputs]
+                g.summands = [(op, outputs[c[1]] if isinstance(c, tuple) else c, left)
+                              for op, c, left in g.summands]
     checks = [(check, outputs[check.output]) for check in tracer.checks]
     fallback = [(name, outputs[index]) for name, index in tracer.fallback_outputs]
     return ParticleTrace(sites=tracer.sites, checks=checks, fallback=fallback, K=K)

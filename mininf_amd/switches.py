@@ -25,6 +25,8 @@ SWITCHES = {
     "DEFER_GATHER": (True, "leave a model's alpha[group] to the gathered site kernel"),
     "DEFER_SUM": (True, "leave a model's alpha[group] + X @ theta to the gathered linear site "
                         "kernel (needs DEFER_MATMUL and DEFER_GATHER)"),
+    "DEFER_SLOPE": (True, "leave the slope terms beta[group] * x of a model's gathered predictor to "
+                          "the gathered slopes site kernel (needs DEFER_GATHER)"),
     "FUSE_ROWS": (True, "a linear launch draws its minibatch's rows itself"),
     "DRAW_IN_LINEAR": (True, "a linear launch draws the guide's theta itself"),
     "BETA_DGRAD": (False, "compute the Beta implicit-gradient factors on a side stream"),
