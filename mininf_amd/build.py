@@ -19,7 +19,7 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(ROOT, "include")
 SOURCES = [os.path.join(CSRC, name)
            for name in ("sites.hip", "guide.hip", "elbo.hip", "linear.hip", "softmax_linear.hip", "gather_site.hip",
-                        "gather_linear_site.hip", "gather_slopes_site.hip",
+                        "gather_linear_site.hip",
                         "minibatch.hip",
                         "adam.hip", "mvn.hip", "mvn_guide.hip", "lowrank_guide.hip", "lowrank_entropy.hip",
                         "dirichlet.hip", "mixture.hip", "predictive.hip", "elementwise_guide.hip", "peer.hip", "jit.cpp")]

@@ -1,7 +1,8 @@
 // What the group-indexed site kernels share (gather_site.hip: mi_gather_site, gather_linear_site.hip:
-// mi_gather_linear, gather_slopes_site.hip: mi_gather_slopes): the lane's accumulators, what a (group, particle) fixes of a density, the
-// launch's workspace layout and the finishing launches (k_gather_sums, k_gather_tables, defined in
-// gather_site.hip and launched through gs_finish).
+// mi_gather_linear and mi_gather_slopes): the lane's accumulators, the Poisson rows' constants, what
+// a particle and what a (group, particle) fix of a density, the launch's workspace layout and the
+// finishing launches (k_gather_sums, k_gather_tables, defined in gather_site.hip and launched
+// through gs_finish).
 #pragma once
 #include "common.hpp"
 #include "internal.hpp"
@@ -51,6 +52,48 @@ __device__ __forceinline__ float gs_value(const mi_gather_site& L, int64_t row) 
   if (L.value_kind == MI_GATHER_VALUE_INT64)
     return (float)static_cast<const int64_t*>(L.value)[row * L.value_stride_i];
   return static_cast<const float*>(L.value)[row * L.value_stride_i];
+}
+
+// Poisson: the sum of -lgamma(y + 1) over the observed rows of the chunk's sorted rows [j0, j1), to
+// W.rowc[chunk]. It does not depend on the particle: the first particle tile calls this, its KT
+// lanes (kk of them this one) take every KT-th row and meet in a __shfl_xor butterfly.
+__device__ __forceinline__ void gs_poisson_rowc(const mi_gather_site& L, const GsWork& W,
+                                                int64_t chunk, bool cin, int64_t j0, int64_t j1,
+                                                int kk, int KT) {
+  double c = 0.0;
+  for (int64_t j = j0 + kk; j < j1; j += KT) {
+    const int64_t o = L.order[j];
+    const int64_t g = L.sorted_group[j];
+    if (o < 0 || o >= L.N || g < 0 || g >= L.G) continue;
+    if (L.mask != nullptr && L.mask[o * L.mask_stride_i] == 0) continue;
+    const float v = gs_value(L, o);
+    if (v >= 0.0f) c -= (double)lgammaf(v + 1.0f);
+  }
+  for (int offset = KT >> 1; offset > 0; offset >>= 1) c += __shfl_xor(c, offset, kWave);
+  if (cin && kk == 0) W.rowc[chunk] = c;
+}
+
+// The affine terms of a role's predictor eta = shift + mult * p for particle k.
+__device__ __forceinline__ float gs_shift(const mi_gather_role& R, int64_t k) {
+  return R.shift_kind == MI_GATHER_TERM_PARTICLE ? R.shift[k * R.shift_stride_k]
+         : R.shift_kind == MI_GATHER_TERM_CONSTANT ? R.shift_constant : 0.0f;
+}
+
+__device__ __forceinline__ float gs_mult(const mi_gather_role& R, int64_t k) {
+  return R.mult_kind == MI_GATHER_TERM_PARTICLE ? R.mult[k * R.mult_stride_k]
+         : R.mult_kind == MI_GATHER_TERM_CONSTANT ? R.mult_constant : 1.0f;
+}
+
+// What particle k fixes of a role: its kind (GATHER, DATA), the affine terms of a GATHER role's
+// predictor, and the value of a PARTICLE or CONSTANT role.
+__device__ __forceinline__ void gs_role_terms(const mi_gather_role& R, int64_t k, float& shift,
+                                              float& mult, float& fixed, bool& gathered,
+                                              bool& rowdata) {
+  gathered = R.kind == MI_GATHER_GATHER;
+  rowdata = R.kind == MI_GATHER_DATA;
+  shift = gs_shift(R, k);
+  mult = gs_mult(R, k);
+  fixed = R.kind == MI_GATHER_PARTICLE ? R.data[k * R.stride_k] : R.constant;
 }
 
 // What a (group, particle) fixes of the density, and the row's step.

@@ -54,34 +54,14 @@ __global__ __launch_bounds__(kGsThreads) void k_gather_site(const mi_gather_site
   uint32_t fl = 0u;
 
   // ---- Poisson: the chunk's sum of -lgamma(y + 1) over its observed rows, by the first tile ------
-  if (FAMILY == MI_POISSON && blockIdx.y == 0) {
-    double c = 0.0;
-    for (int64_t j = j0 + kk; j < j1; j += KT) {
-      const int64_t o = ord[j];
-      const int64_t g = sg[j];
-      if (o < 0 || o >= N || g < 0 || g >= G) continue;
-      if (L.mask != nullptr && L.mask[o * L.mask_stride_i] == 0) continue;
-      const float v = gs_value(L, o);
-      if (v >= 0.0f) c -= (double)lgammaf(v + 1.0f);
-    }
-    for (int offset = KT >> 1; offset > 0; offset >>= 1) c += __shfl_xor(c, offset, kWave);
-    if (cin && kk == 0) W.rowc[chunk] = c;
-  }
+  if (FAMILY == MI_POISSON && blockIdx.y == 0) gs_poisson_rowc(L, W, chunk, cin, j0, j1, kk, KT);
 
   // ---- what the particle fixes -------------------------------------------------------------------
   float shift[2], mult[2], praw[2] = {0.0f, 0.0f}, fixed[2];
   bool gathered[2], rowdata[2];
 #pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const mi_gather_role& R = L.role[r];
-    gathered[r] = R.kind == MI_GATHER_GATHER;
-    rowdata[r] = R.kind == MI_GATHER_DATA;
-    shift[r] = R.shift_kind == MI_GATHER_TERM_PARTICLE ? R.shift[k * R.shift_stride_k]
-               : R.shift_kind == MI_GATHER_TERM_CONSTANT ? R.shift_constant : 0.0f;
-    mult[r] = R.mult_kind == MI_GATHER_TERM_PARTICLE ? R.mult[k * R.mult_stride_k]
-              : R.mult_kind == MI_GATHER_TERM_CONSTANT ? R.mult_constant : 1.0f;
-    fixed[r] = R.kind == MI_GATHER_PARTICLE ? R.data[k * R.stride_k] : R.constant;
-  }
+  for (int r = 0; r < 2; ++r)
+    gs_role_terms(L.role[r], k, shift[r], mult[r], fixed[r], gathered[r], rowdata[r]);
   const bool anydata = rowdata[0] || rowdata[1];
   const bool head_shared = cin && j0 > 0 && sg[j0 - 1] == sg[j0];
   const bool tail_shared = cin && j1 < N && sg[j1] == sg[j1 - 1];
@@ -249,21 +229,8 @@ __global__ __launch_bounds__(256) void k_gather_tables(const mi_gather_site L, c
   const int64_t k = blockIdx.y;
   if (g >= L.G) return;
   const int32_t* __restrict__ const sg = L.sorted_group;
-  // [lo, hi): the sorted rows of group g
-  int64_t a = 0, b = L.N;
-  while (a < b) {
-    const int64_t m = (a + b) >> 1;
-    if ((int64_t)sg[m] < g) a = m + 1;
-    else b = m;
-  }
-  const int64_t lo = a;
-  b = L.N;
-  while (a < b) {
-    const int64_t m = (a + b) >> 1;
-    if ((int64_t)sg[m] <= g) a = m + 1;
-    else b = m;
-  }
-  const int64_t hi = a;
+  int64_t lo, hi;
+  gs_group_rows(sg, L.N, g, lo, hi);
   float* const dst = W.dtable[r] + k * L.G + g;
   if (lo == hi) {
     *dst = 0.0f;
@@ -271,9 +238,7 @@ __global__ __launch_bounds__(256) void k_gather_tables(const mi_gather_site L, c
   }
   const int64_t c0 = lo / kGsRows, c1 = (hi - 1) / kGsRows;
   if (c0 == c1) return;   // stored by the chunk that holds all its rows
-  const mi_gather_role& R = L.role[r];
-  const float mult = R.mult_kind == MI_GATHER_TERM_PARTICLE ? R.mult[k * R.mult_stride_k]
-                     : R.mult_kind == MI_GATHER_TERM_CONSTANT ? R.mult_constant : 1.0f;
+  const float mult = gs_mult(L.role[r], k);
   // the chunk where the group starts left its tail, every later one its head
   double S = (double)W.slab[(((int64_t)r * 2 + 1) * W.nchunk + c0) * L.K + k];
   for (int64_t c = c0 + 1; c <= c1; ++c) S += (double)W.slab[(((int64_t)r * 2) * W.nchunk + c) * L.K + k];

@@ -7,14 +7,11 @@ A case is a case of tests/gather_site_reference.py (role 0 gathered) with X [N, 
 (float32), ``x_layout`` (how X lies in memory, see :func:`x_tensor`) and ``theta_strided``; ``null``
 may name "dtheta" too.
 
-reference():    fp64, as gather_site_reference.reference with role 0's eta extended by the linear
-                term, and "dtheta": (g0 * scale * sum_i m_i * deta0_i * X[i, j], its sum of absolute
+reference() and float32_restatement() are those of tests/gather_slopes_reference.py (one kernel,
+csrc/gather_linear_site.hip, evaluates both sites) for a case without slopes:
+reference():    fp64, with "dtheta": (g0 * scale * sum_i m_i * deta0_i * X[i, j], its sum of absolute
                 terms divided by g0), deta0 the per-row quantity that is summed into role 0's dtable.
-float32_restatement(): the kernel's arithmetic in float32 numpy (csrc/gather_linear_site.hip): eta0
-                as fmaf(mult, p, shift) followed by one fmaf per column of X in order, the row's
-                terms derived per row, dtheta as a float sum over each batch of 8 sorted rows
-                folded into a float over the chunk of ROWS rows, the chunks' parts added in fp64;
-                everything else as gather_site_reference.float32_restatement.
+float32_restatement(): the kernel's arithmetic in float32 numpy.
 launch():       one call over poisoned buffers with guard bands around every output.
 """
 import ctypes
@@ -22,8 +19,8 @@ import ctypes
 import numpy as np
 
 from mininf_amd import _native as nat
-from tests.gather_site_reference import (GUARD, HALF_LOG_2PI, ROWS, _names as _site_names, _sigmoid,
-                                         _term, describe, lgamma, sort_plan, tensors_of, wrap)
+from tests.gather_site_reference import (GUARD, ROWS, _names as _site_names, describe, sort_plan,
+                                         tensors_of)
 
 BATCH = 8   # kGsBatch: rows per fold of the float sums
 X_LAYOUTS = ("plain", "slice", "slice1", "offset", "transposed")
@@ -37,173 +34,14 @@ def _names(case):
 
 
 def reference(case):
-    K, N, G = case["K"], case["N"], case["G"]
-    idx = wrap(case["index"], G)
-    v = np.asarray(case["value"], np.float64)[None, :]
-    m = np.ones(N) if case["mask"] is None else np.asarray(case["mask"], np.float64)
-    m = m[None, :]
-    v = np.where(m != 0, v, 0.0)
-    scale, g0 = case["site_scale"], case["g0"]
-    X = np.asarray(case["X"], np.float64)
-    X = np.where(m.T != 0, X, 0.0)   # (a masked-out row adds nothing, whatever it holds)
-    theta = np.asarray(case["theta"], np.float64)
-    a, eta, praw = [None, None], [None, None], [None, None]
-    with np.errstate(all="ignore"):
-        for r, role in enumerate(case["roles"]):
-            if role[0] == "gather":
-                praw[r] = role[1].astype(np.float64)[:, idx]
-                eta[r] = _term(role[2], K, 0.0)[:, None] + _term(role[3], K, 1.0)[:, None] * praw[r]
-                if r == 0:
-                    eta[r] = eta[r] + theta @ X.T
-                a[r] = np.exp(eta[r]) if role[4] == "exp" else eta[r]
-            elif role[0] == "particle":
-                a[r] = np.asarray(role[1], np.float64)[:, None] * np.ones((1, N))
-            elif role[0] == "data":
-                a[r] = np.asarray(role[1], np.float64)[None, :] * np.ones((K, 1))
-            else:
-                a[r] = np.full((K, N), float(role[1]))
-        family = case["family"]
-        if family == "normal":
-            diff = v - a[0]
-            parts = [-diff ** 2 / (2 * a[1] ** 2), -np.log(a[1]), np.full((K, N), -HALF_LOG_2PI)]
-            d = [diff / a[1] ** 2, (diff ** 2 / a[1] ** 2 - 1) / a[1]]
-        elif family == "bernoulli":
-            parts = [v * a[0], -np.logaddexp(0.0, a[0])]
-            d = [v - _sigmoid(a[0]), None]
-        else:
-            parts = [v * eta[0], -a[0], -lgamma(np.where(v >= 0, v, 0.0) + 1) * np.ones((K, 1))]
-            d = [v / a[0] - 1, None]
-        parts = [np.where(m != 0, p, 0.0) for p in parts]
-        out = {"total": (scale * sum(parts).sum(1),
-                         abs(scale) * sum(np.abs(p) for p in parts).sum(1))}
-        for r, role in enumerate(case["roles"]):
-            if d[r] is None:
-                continue
-            dr = np.where(m != 0, d[r], 0.0)
-            if role[0] == "particle":
-                out[f"role{r}"] = (g0 * scale * dr.sum(1), abs(scale) * np.abs(dr).sum(1))
-            if role[0] != "gather":
-                continue
-            deta = np.where(m != 0, dr * (a[r] if role[4] == "exp" else 1.0), 0.0)
-            mult = _term(role[3], K, 1.0)[:, None]
-            onehot = (idx[:, None] == np.arange(G)[None, :]).astype(np.float64)   # [N, G]
-            out[f"role{r}"] = (g0 * scale * mult * (deta @ onehot),
-                               abs(scale) * np.abs(mult) * (np.abs(deta) @ onehot))
-            if isinstance(role[2], np.ndarray):
-                out[f"shift{r}"] = (g0 * scale * deta.sum(1), abs(scale) * np.abs(deta).sum(1))
-            if isinstance(role[3], np.ndarray):
-                out[f"mult{r}"] = (g0 * scale * (deta * praw[r]).sum(1),
-                                   abs(scale) * np.abs(deta * praw[r]).sum(1))
-            if r == 0:
-                out["dtheta"] = (g0 * scale * (deta @ X), abs(scale) * (np.abs(deta) @ np.abs(X)))
-    return out
+    from tests.gather_slopes_reference import reference as with_slopes   # (it imports this module)
+    return with_slopes(case)
 
 
 def float32_restatement(case):
     """name -> value by the kernel's float32 formula (see the module docstring)."""
-    f = np.float32
-    K, N, G, P = case["K"], case["N"], case["G"], case["P"]
-    order, sg = sort_plan(case["index"], G)
-    sg = sg.astype(np.int64)
-    v = np.asarray(case["value"]).astype(f)[order][None, :]
-    m = np.ones(N, bool) if case["mask"] is None else np.asarray(case["mask"], bool)[order]
-    X = np.asarray(case["X"], f)[order]          # sorted rows
-    theta = np.asarray(case["theta"], f)
-    scale, g0 = case["site_scale"], case["g0"]
-    gscale = float(f(g0)) * scale
-    a, eta, praw, chain = [None, None], [None, None], [None, None], [1.0, 1.0]
-    fma = lambda x, y, z: (x.astype(np.float64) * y.astype(np.float64) + z.astype(np.float64)).astype(f)
-    with np.errstate(all="ignore"):
-        for r, role in enumerate(case["roles"]):
-            if role[0] == "gather":
-                praw[r] = role[1].astype(f)[:, sg]
-                shift = _term(role[2], K, 0.0).astype(f)[:, None]
-                mult = _term(role[3], K, 1.0).astype(f)[:, None]
-                eta[r] = fma(np.broadcast_to(mult, praw[r].shape), praw[r],
-                             np.broadcast_to(shift, praw[r].shape))
-                if r == 0:
-                    for j in range(P):   # one fmaf per column, in order
-                        eta[r] = fma(np.broadcast_to(X[None, :, j], eta[r].shape),
-                                     np.broadcast_to(theta[:, j:j + 1], eta[r].shape), eta[r])
-                a[r] = eta[r]
-                if role[4] == "exp":
-                    a[r] = np.exp(eta[r]).astype(f)
-                    if case["family"] != "poisson":
-                        chain[r] = a[r]
-            elif role[0] == "particle":
-                a[r] = np.broadcast_to(np.asarray(role[1], f)[:, None], (K, N))
-            elif role[0] == "data":
-                a[r] = np.broadcast_to(np.asarray(role[1], f)[order][None, :], (K, N))
-            else:
-                a[r] = np.full((K, N), f(role[1]))
-        family = case["family"]
-        rowc = 0.0
-        if family == "normal":
-            inv = (f(1) / a[1]).astype(f)
-            inv2 = (inv * inv).astype(f)
-            c2 = (-(np.log(a[1]).astype(f) + f(HALF_LOG_2PI))).astype(f)
-            diff = (v - a[0]).astype(f)
-            lp = fma(((f(-0.5) * inv2).astype(f) * diff).astype(f), diff, c2)
-            g = (diff * inv2).astype(f)
-            d = [g, (fma(diff, g, np.full_like(g, -1)) * inv).astype(f)]
-        elif family == "bernoulli":
-            t = np.exp(-np.abs(a[0])).astype(f)
-            u = (f(1) + t).astype(f)
-            c0 = (np.maximum(a[0], f(0)) + np.log1p(t).astype(f)).astype(f)
-            sig = np.where(a[0] >= 0, f(1) / u, t / u).astype(f)
-            lp = fma(a[0], np.broadcast_to(v, a[0].shape), -c0)
-            d = [(v - sig).astype(f), None]
-        else:
-            lp = fma(np.broadcast_to(v, a[0].shape), eta[0], -a[0])
-            d = [(v - a[0]).astype(f), None]
-            vv = v[0].astype(np.float64)
-            rowc = -(lgamma(np.where(vv >= 0, vv, 0.0) + 1).astype(f).astype(np.float64) * m).sum()
-        lp = np.where(m[None, :], lp.astype(np.float64), 0.0)
-    out = {"total": scale * (lp.sum(1) + rowc)}
-    starts = np.r_[0, np.flatnonzero(np.diff(sg)) + 1, N]
-    for r, role in enumerate(case["roles"]):
-        if d[r] is None:
-            continue
-        if role[0] == "particle":
-            out[f"role{r}"] = gscale * np.where(m[None, :], d[r].astype(np.float64), 0.0).sum(1)
-        if role[0] != "gather":
-            continue
-        de32 = (d[r] * chain[r]).astype(f)
-        deta = np.where(m[None, :], de32.astype(np.float64), 0.0)
-        mult = _term(role[3], K, 1.0).astype(f).astype(np.float64)
-        dtable = np.zeros((K, G))
-        S_all = np.zeros((K, N))
-        for s0, s1 in zip(starts[:-1], starts[1:]):
-            c0, c1 = s0 // ROWS, (s1 - 1) // ROWS
-            if c0 == c1:
-                S = deta[:, s0:s1].sum(1)
-            else:   # the chunks' parts pass through float32 (the slab)
-                edges = [s0] + [c * ROWS for c in range(c0 + 1, c1 + 1)] + [s1]
-                S = sum(deta[:, e0:e1].sum(1).astype(f).astype(np.float64)
-                        for e0, e1 in zip(edges[:-1], edges[1:]))
-            dtable[:, sg[s0]] = gscale * mult * S
-            S_all[:, s0] = deta[:, s0:s1].sum(1)
-        out[f"role{r}"] = dtable
-        if isinstance(role[2], np.ndarray):
-            out[f"shift{r}"] = gscale * S_all.sum(1)
-        if isinstance(role[3], np.ndarray):
-            out[f"mult{r}"] = gscale * (S_all * praw[r].astype(np.float64)).sum(1)
-        if r == 0:
-            # a float over a batch of BATCH rows, folded into a float over the chunk, the chunks
-            # in fp64
-            dtheta = np.zeros((K, P))
-            for c0 in range(0, N, ROWS):
-                hi = np.zeros((K, P), f)
-                for b0 in range(c0, min(N, c0 + ROWS), BATCH):
-                    lo = np.zeros((K, P), f)
-                    for i in range(b0, min(N, c0 + ROWS, b0 + BATCH)):
-                        if m[i]:
-                            lo = fma(np.broadcast_to(de32[:, i:i + 1], lo.shape),
-                                     np.broadcast_to(X[i][None, :], lo.shape), lo)
-                    hi = (hi + lo).astype(f)
-                dtheta += hi.astype(np.float64)
-            out["dtheta"] = gscale * dtheta
-    return out
+    from tests.gather_slopes_reference import float32_restatement as with_slopes
+    return with_slopes(case)
 
 
 def x_tensor(case, device):

@@ -8,16 +8,22 @@ A case is a case of tests/gather_linear_reference.py (P may be 0: X [N, 0], thet
 in memory, see :func:`z_tensors`); ``null`` may name "slope0".."slope3" too, and ``null_slopes``
 hands the launch a NULL dslope array.
 
-reference():    fp64, as gather_linear_reference.reference with role 0's eta extended by the slope
-                terms, and "slope<s>": (g0 * scale * sum_{i in g} m_i * deta0_i * z_s[i], its sum of
-                absolute terms divided by g0), deta0 the per-row quantity that is summed into role
-                0's dtable and into dtheta.
-float32_restatement(): the kernel's arithmetic in float32 numpy (csrc/gather_slopes_site.hip): eta0
+reference() and float32_restatement() take a case without ``slopes`` as one with none: they are the
+references of tests/gather_linear_reference.py too.
+
+reference():    fp64, as gather_site_reference.reference with role 0's eta extended by the slope
+                terms and the linear term; "dtheta": (g0 * scale * sum_i m_i * deta0_i * X[i, j], its
+                sum of absolute terms divided by g0) and "slope<s>": (g0 * scale * sum_{i in g} m_i *
+                deta0_i * z_s[i], likewise), deta0 the per-row quantity that is summed into role 0's
+                dtable.
+float32_restatement(): the kernel's arithmetic in float32 numpy (csrc/gather_linear_site.hip): eta0
                 as fmaf(mult, p, shift), then one fmaf(beta_s, z_s, eta) per slope in order, then
-                one fmaf per column of X in order; dslope as fmaf(de, z, lo) over each batch of 8
-                sorted rows of the chunk, the batches folded into a double per group (a group's
-                parts rounded to float32 where the kernel leaves them in its slab); everything
-                else as gather_linear_reference.float32_restatement.
+                one fmaf per column of X in order, the row's terms derived per row; dtheta as a
+                float sum over each batch of 8 sorted rows folded into a float over the chunk of
+                ROWS rows, the chunks' parts added in fp64; dslope as fmaf(de, z, lo) over each
+                batch of 8 sorted rows of the chunk, the batches folded into a double per group (a
+                group's parts rounded to float32 where the kernel leaves them in its slab);
+                everything else as gather_site_reference.float32_restatement.
 launch():       one call over poisoned buffers with guard bands around every output.
 """
 import ctypes
@@ -52,7 +58,8 @@ def reference(case):
     X = np.asarray(case["X"], np.float64).reshape(N, case["P"])
     X = np.where(m.T != 0, X, 0.0)   # (a masked-out row adds nothing, whatever it holds)
     theta = np.asarray(case["theta"], np.float64).reshape(K, case["P"])
-    zs = [np.where(m[0] != 0, np.asarray(z, np.float64), 0.0) for _, z in case["slopes"]]
+    slopes = case.get("slopes", [])
+    zs = [np.where(m[0] != 0, np.asarray(z, np.float64), 0.0) for _, z in slopes]
     a, eta, praw = [None, None], [None, None], [None, None]
     with np.errstate(all="ignore"):
         for r, role in enumerate(case["roles"]):
@@ -60,7 +67,7 @@ def reference(case):
                 praw[r] = role[1].astype(np.float64)[:, idx]
                 eta[r] = _term(role[2], K, 0.0)[:, None] + _term(role[3], K, 1.0)[:, None] * praw[r]
                 if r == 0:
-                    for (beta, _), z in zip(case["slopes"], zs):
+                    for (beta, _), z in zip(slopes, zs):
                         eta[r] = eta[r] + beta.astype(np.float64)[:, idx] * z[None, :]
                     eta[r] = eta[r] + theta @ X.T
                 a[r] = np.exp(eta[r]) if role[4] == "exp" else eta[r]
@@ -120,8 +127,9 @@ def float32_restatement(case):
     m = np.ones(N, bool) if case["mask"] is None else np.asarray(case["mask"], bool)[order]
     X = np.asarray(case["X"], f).reshape(N, P)[order]          # sorted rows
     theta = np.asarray(case["theta"], f).reshape(K, P)
+    slopes = case.get("slopes", [])
     # (a masked-out row reads no z: the kernel holds 0 there)
-    zs = [np.where(m, np.asarray(z, f)[order], f(0)) for _, z in case["slopes"]]
+    zs = [np.where(m, np.asarray(z, f)[order], f(0)) for _, z in slopes]
     scale, g0 = case["site_scale"], case["g0"]
     gscale = float(f(g0)) * scale
     a, eta, praw, chain = [None, None], [None, None], [None, None], [1.0, 1.0]
@@ -135,7 +143,7 @@ def float32_restatement(case):
                 eta[r] = fma(np.broadcast_to(mult, praw[r].shape), praw[r],
                              np.broadcast_to(shift, praw[r].shape))
                 if r == 0:
-                    for (beta, _), z in zip(case["slopes"], zs):   # one fmaf per slope, in order
+                    for (beta, _), z in zip(slopes, zs):   # one fmaf per slope, in order
                         eta[r] = fma(beta.astype(f)[:, sg], np.broadcast_to(z[None, :], eta[r].shape),
                                      eta[r])
                     for j in range(P):   # one fmaf per column, in order

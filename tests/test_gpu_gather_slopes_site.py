@@ -1,5 +1,5 @@
 """
-mi_gather_slopes_forward (csrc/gather_slopes_site.hip) point by point against the fp64 reference of
+mi_gather_slopes_forward (csrc/gather_linear_site.hip) point by point against the fp64 reference of
 tests/gather_slopes_reference.py, through the C ABI, over poisoned and guarded buffers.
 
 Bounds (those of tests/test_gpu_gather_site.py):

@@ -1,5 +1,5 @@
 """
-Kernel-level times of mi_gather_slopes_forward (csrc/gather_slopes_site.hip) through the C ABI, beside
+Kernel-level times of mi_gather_slopes_forward (csrc/gather_linear_site.hip) through the C ABI, beside
 mi_gather_linear_forward (P >= 1) or mi_gather_site_forward (P = 0) on the same rows without the
 slope terms and beside the step's arithmetic as torch does it on the materialised predictor ([K, N]
 gathers and products, the density, and autograd's scatter-adds).
