@@ -39,8 +39,8 @@ from ..particles import ParticleTrace, SiteRecord
 from ._operands import (FAMILY_CODES, _INTEGER_VALUED, _ONE_PARAMETER, _Operand, _View, _collapse,
                         _float, _to_device)
 from ._groups import _QUERY_ADDRESS, _GroupLauncher, _SiteGroupFn
-from ._rows import (_CategoricalFn, _DirichletFn, _MixtureNormalFn, _run_categorical,
-                    _run_dirichlet, _run_mixture_normal, _run_row_site, row_site_fn)
+from ._rows import (_RowSiteFn, _run_categorical, _run_dirichlet, _run_mixture_normal,
+                    _run_row_site)
 from ._linear import _LinearLauncher, _LinearSiteFn
 from ._held import (PendingGrad, _FUSED_ADAM_MAX_NUMEL, _PendingStep, _defer_step,
                     attach_optimizer, discard_pending_step, flush_pending_step, grad_meta,
@@ -65,7 +65,7 @@ def log_joint(trace: ParticleTrace, g0: float, device: torch.device) -> LogJoint
     pending: List[Tuple[str, dict, List[SiteRecord]]] = []
     for site, params, val, mask in categorical:
         holder: dict = {}
-        totals.append(row_site_fn(site).apply(site, holder, g0, *params, val, mask))
+        totals.append(_RowSiteFn.apply(site, holder, g0, *params, val, mask))
         pending.append((site.family, holder, [site]))
     for linear in linears:
         holder = {}

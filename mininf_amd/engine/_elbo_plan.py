@@ -13,6 +13,7 @@ from .. import _native as nat
 from .. import guide, switches
 from ._absorb import EntropyFactor, _Absorbed
 from ._held import _defer_step, flush_pending_step
+from .gather import _GatherLauncher
 from ._linear import _LinearLauncher
 from ._rows import _run_row_site
 
@@ -436,6 +437,9 @@ class _ElboPlan:
         mi_gather_linear_forward (no [K, N] product either); gathered_slope_sites: those of the
         gathered sites with slope terms ``beta[group] * z``, on mi_gather_slopes_forward.
         """
+        # (a softmax-linear site's launcher counts nowhere here)
+        gathered = [site.launcher for site, _, _, _ in self.categorical
+                    if isinstance(site.launcher, _GatherLauncher) and site.launcher.launches > 0]
         return {
             "folded_priors": sum(l.prior is not None for l in self.launchers) +
             sum(l.prior is not None for l in self.linears),
@@ -452,14 +456,9 @@ class _ElboPlan:
             "lowrank_draws": guide.lowrank_draws(),
             "elementwise_draws": guide.elementwise_draws(),
             "lowrank_entropies": 0,   # set by the loss, which evaluates the rest's entropies
-            "gathered_sites": sum(site.gather is not None and site.gather.launches > 0
-                                  for site, _, _, _ in self.categorical),
-            "gathered_linear_sites": sum(site.gather is not None and site.gather.linear and
-                                         site.gather.launches > 0
-                                         for site, _, _, _ in self.categorical),
-            "gathered_slope_sites": sum(site.gather is not None and site.gather.slopes and
-                                        site.gather.launches > 0
-                                        for site, _, _, _ in self.categorical),
+            "gathered_sites": len(gathered),
+            "gathered_linear_sites": sum(launcher.linear for launcher in gathered),
+            "gathered_slope_sites": sum(launcher.slopes for launcher in gathered),
         }
 
     def _reduce_ok(self, assume=None) -> bool:

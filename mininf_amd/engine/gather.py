@@ -4,11 +4,12 @@ gather ``alpha[group]`` of a per-particle table [K, G], fused (``mi_gather_site_
 gather was deferred by :mod:`mininf_amd.linear`), and those whose first role also has fixed
 effects, ``alpha[group] + X @ theta`` (``mi_gather_linear_forward``: theta [K, P] joins the
 launcher's parameters) or varying slopes, ``alpha[group] + beta[group] * z [+ X @ theta]``
-(``mi_gather_slopes_forward``: the slope tables [K, G] join the parameters too). Such a site is planned as a row site -- an entry
-(site, parameters, value, mask) of the planner's categorical list whose record carries its launcher
-(``site.gather``) -- so the ELBO plan, ``log_joint`` and ``LogLikelihoodLoss`` take it like any row
-site: its speculative gradients are dense in every parameter (the tables [K, G], per-particle
-roles, shifts and mults [K]), and it declines absorption like every row site.
+(``mi_gather_slopes_forward``: the slope tables [K, G] join the parameters too). Such a site is
+planned as a row site -- an entry (site, parameters, value, mask) of the planner's categorical list
+whose record carries its launcher (``site.launcher``, run by ``engine._rows._run_row_site`` under
+the row sites' one contract) -- so the ELBO plan, ``log_joint`` and ``LogLikelihoodLoss`` take it
+like any row site: its speculative gradients are dense in every parameter (the tables [K, G],
+per-particle roles, shifts and mults [K]), and it declines absorption like every row site.
 
 The kernel reads the rows sorted by group: :func:`index_plan` turns the model's index into
 (order, sorted_group) once per index tensor.
@@ -26,6 +27,7 @@ from .. import data
 from ..linear import put_back as _materialise   # (the gather back as the model wrote it)
 from ..particles import SiteRecord
 from ._operands import FAMILY_CODES, _collapse, _to_device
+from ._rows import _buffers
 
 # Index plans by (data pointer, shape, stride, dtype, device, G): (weakref to the index, its
 # version, (order, sorted_group) or None for an index out of range). The sort and the range
@@ -110,35 +112,46 @@ class _GatherLauncher:
         self.linear = roles[0].X is not None   # an X @ theta term (mi_gather_linear_forward)
         self.slopes = bool(roles[0].slope_params)   # mi_gather_slopes_forward
 
-    def describe_slopes(self, params: Tuple[torch.Tensor, ...], g0: float) -> nat.GatherSlopes:
-        M = nat.GatherSlopes()
-        if self.linear:
-            M.linear = self.describe_linear(params, g0)
-        else:
-            M.linear.site = self.describe(params, g0)
+    def describe(self, params: Tuple[torch.Tensor, ...], g0: float, grad_ptr):
+        """
+        The launch's descriptor: (the outermost struct, the ``nat.GatherSite`` inside it, the stem
+        of the library's entry points for it, the forward's arguments after the role gradients).
+        ``grad_ptr(where)``: the address of ``params[where]``'s gradient, or None.
+        """
         role = self.roles[0]
+        if not self.linear and not self.slopes:
+            L = nat.GatherSite()
+            self._describe_site(L, params, g0)
+            return L, L, "mi_gather_site", ()
+        M = nat.GatherSlopes() if self.slopes else nat.GatherLinear()
+        linear = M.linear if self.slopes else M   # (P = 0 where the slopes have no X @ theta)
+        site = linear.site
+        self._describe_site(site, params, g0)
+        dtheta = None
+        if self.linear:
+            X, theta = role.X, params[role.theta_param]
+            linear.P = int(X.shape[1])
+            linear.x = X.data_ptr()
+            linear.x_stride_i, linear.x_stride_j = X.stride()
+            linear.theta = theta.data_ptr()
+            linear.theta_stride_k, linear.theta_stride_j = theta.stride()
+            dtheta = grad_ptr(role.theta_param)   # [K, P] contiguous, every entry written
+        if not self.slopes:
+            return M, site, "mi_gather_linear", (dtheta,)
         M.S = len(role.slope_params)
+        dslope = (nat.c_vp * nat.GATHER_MAX_SLOPES)()
         for s, (where, z) in enumerate(zip(role.slope_params, role.slope_z)):
             table = params[where]
             M.slope[s].table = table.data_ptr()
             M.slope[s].stride_k, M.slope[s].stride_g = table.stride()
             M.slope[s].z = z.data_ptr()
             M.slope[s].z_stride_i = z.stride(0)
-        return M
+            dslope[s] = grad_ptr(where)   # [K, G] contiguous, every entry written
+        return M, site, "mi_gather_slopes", (dtheta, dslope)
 
-    def describe_linear(self, params: Tuple[torch.Tensor, ...], g0: float) -> nat.GatherLinear:
-        M = nat.GatherLinear()
-        M.site = self.describe(params, g0)
-        X, theta = self.roles[0].X, params[self.roles[0].theta_param]
-        M.P = int(X.shape[1])
-        M.x = X.data_ptr()
-        M.x_stride_i, M.x_stride_j = X.stride()
-        M.theta = theta.data_ptr()
-        M.theta_stride_k, M.theta_stride_j = theta.stride()
-        return M
-
-    def describe(self, params: Tuple[torch.Tensor, ...], g0: float) -> nat.GatherSite:
-        L = nat.GatherSite()
+    def _describe_site(self, L: nat.GatherSite, params: Tuple[torch.Tensor, ...],
+                       g0: float) -> None:
+        """Fill ``L``, the site without its linear and slope terms."""
         L.K, L.N, L.G = self.K, self.N, self.G
         L.family = FAMILY_CODES[self.site.family]
         for r, role in enumerate(self.roles):
@@ -179,80 +192,46 @@ class _GatherLauncher:
             L.mask_stride_i = self.mask.stride(0)
         L.grad_scale = g0
         L.site_scale = self.site.scale
-        return L
 
     def run(self, params: Tuple[torch.Tensor, ...], g0: float,
             flags: Optional[torch.Tensor] = None):
         """(total [K], the speculative gradients of ``params`` -- None where none is needed --,
-        flags [1])."""
+        no dvalue, flags [1])."""
         device = self.device
-        L = self.describe_slopes(params, g0) if self.slopes else \
-            self.describe_linear(params, g0) if self.linear else self.describe(params, g0)
-        if flags is None:
-            flags = torch.empty(1, dtype=torch.int32, device=device)
-        elif self.slopes:
-            L.linear.site.options |= nat.GROUP_FLAGS_ZEROED
-        elif self.linear:
-            L.site.options |= nat.GROUP_FLAGS_ZEROED
-        else:
-            L.options |= nat.GROUP_FLAGS_ZEROED
         grads: List[Optional[torch.Tensor]] = [None] * len(params)
+
+        def grad_ptr(where: int) -> Optional[int]:
+            if where < 0 or not params[where].requires_grad:
+                return None
+            # (every entry written; a per-particle parameter's in its own shape)
+            grads[where] = torch.empty(tuple(params[where].shape), dtype=torch.float32,
+                                       device=device)
+            return grads[where].data_ptr()
+
         G = nat.GatherGrads()
         for r, role in enumerate(self.roles):
-            for field, where in ((G.role, role.param), (G.shift, role.shift_param),
-                                 (G.mult, role.mult_param)):
-                if where >= 0 and params[where].requires_grad:
-                    # (every entry written; a per-particle parameter's in its own shape)
-                    grads[where] = torch.empty(tuple(params[where].shape), dtype=torch.float32,
-                                               device=device)
-                    field[r] = grads[where].data_ptr()
+            G.role[r] = grad_ptr(role.param)
+            G.shift[r] = grad_ptr(role.shift_param)
+            G.mult[r] = grad_ptr(role.mult_param)
+        L, site, stem, extra = self.describe(params, g0, grad_ptr)
+        if flags is not None:
+            site.options |= nat.GROUP_FLAGS_ZEROED
         size = ctypes.c_size_t()
         lib = nat.lib()
-        total = torch.empty(self.K, dtype=torch.float32, device=device)
-        dtheta = None
-        if self.linear:
-            where = self.roles[0].theta_param
-            if params[where].requires_grad:   # [K, P] contiguous, every entry written
-                grads[where] = torch.empty(tuple(params[where].shape), dtype=torch.float32,
-                                           device=device)
-                dtheta = grads[where].data_ptr()
-        if self.slopes:
-            dslope = (nat.c_vp * nat.GATHER_MAX_SLOPES)()
-            for s, where in enumerate(self.roles[0].slope_params):
-                if params[where].requires_grad:   # [K, G] contiguous, every entry written
-                    grads[where] = torch.empty(tuple(params[where].shape), dtype=torch.float32,
-                                               device=device)
-                    dslope[s] = grads[where].data_ptr()
-            code = lib.mi_gather_slopes_workspace_bytes(ctypes.byref(L), ctypes.byref(size))
-            if code == nat.MI_EUNSUPPORTED:
-                return self._materialised(params, g0, flags)
-            nat.check(code, "mi_gather_slopes_workspace_bytes")
-            workspace = torch.empty(max(1, size.value), dtype=torch.uint8, device=device)
-            code = lib.mi_gather_slopes_forward(ctypes.byref(L), workspace.data_ptr(), size.value,
-                                                total.data_ptr(), ctypes.byref(G), dtheta, dslope,
-                                                flags.data_ptr(), nat.stream_handle(device))
-        elif self.linear:
-            code = lib.mi_gather_linear_workspace_bytes(ctypes.byref(L), ctypes.byref(size))
-            if code == nat.MI_EUNSUPPORTED:
-                return self._materialised(params, g0, flags)
-            nat.check(code, "mi_gather_linear_workspace_bytes")
-            workspace = torch.empty(max(1, size.value), dtype=torch.uint8, device=device)
-            code = lib.mi_gather_linear_forward(ctypes.byref(L), workspace.data_ptr(), size.value,
-                                                total.data_ptr(), ctypes.byref(G), dtheta,
-                                                flags.data_ptr(), nat.stream_handle(device))
-        else:
-            nat.check(lib.mi_gather_site_workspace_bytes(ctypes.byref(L), ctypes.byref(size)),
-                      "mi_gather_site_workspace_bytes")
-            workspace = torch.empty(max(1, size.value), dtype=torch.uint8, device=device)
-            code = lib.mi_gather_site_forward(ctypes.byref(L), workspace.data_ptr(), size.value,
-                                              total.data_ptr(), ctypes.byref(G), flags.data_ptr(),
-                                              nat.stream_handle(device))
+        code = getattr(lib, stem + "_workspace_bytes")(ctypes.byref(L), ctypes.byref(size))
+        # (only the linear and slopes queries decline a site; the plain one's codes are all errors)
+        if code == nat.MI_EUNSUPPORTED and stem != "mi_gather_site":
+            return self._materialised(params, g0, flags)
+        nat.check(code, stem + "_workspace_bytes")
+        workspace, total, words = _buffers(size.value, self.K, device, flags)
+        code = getattr(lib, stem + "_forward")(
+            ctypes.byref(L), workspace.data_ptr(), size.value, total.data_ptr(), ctypes.byref(G),
+            *extra, words.data_ptr(), nat.stream_handle(device))
         if code == nat.MI_EUNSUPPORTED:
             return self._materialised(params, g0, flags)
-        nat.check(code, "mi_gather_slopes_forward" if self.slopes else
-                  "mi_gather_linear_forward" if self.linear else "mi_gather_site_forward")
+        nat.check(code, stem + "_forward")
         self.launches += 1
-        return total, tuple(grads), flags
+        return total, tuple(grads), None, words
 
     def _predictor(self, r: int, params: Tuple[torch.Tensor, ...]) -> torch.Tensor:
         """Role r as the model would have computed it: [K, N] (or a broadcastable view)."""
@@ -274,9 +253,13 @@ class _GatherLauncher:
                        else role.shift, params[role.mult_param] if role.mult_param >= 0
                        else role.mult, role.link == nat.GATHER_LINK_EXP, linear)
 
-    def _materialised(self, params: Tuple[torch.Tensor, ...], g0: float, flags: torch.Tensor):
-        """The launch the library declined, through torch on the materialised gather."""
+    def _materialised(self, params: Tuple[torch.Tensor, ...], g0: float,
+                      flags: Optional[torch.Tensor]):
+        """The launch the library declined, through torch on the materialised gather: what
+        :meth:`run` returns (torch validates nothing here: with no ``flags`` given, a zero word)."""
         from torch.distributions import Bernoulli, Normal, Poisson
+        if flags is None:
+            flags = torch.zeros(1, dtype=torch.int32, device=self.device)
         leaves = [p.detach().requires_grad_(p.requires_grad) for p in params]
         with torch.enable_grad():
             a = [self._predictor(r, tuple(leaves)) for r in range(2)]
@@ -295,7 +278,7 @@ class _GatherLauncher:
         grads = tuple((next(got) if p.requires_grad else None) for p in leaves)
         grads = tuple(torch.zeros_like(p) if g is None and p.requires_grad else g
                       for g, p in zip(grads, leaves))
-        return total.detach(), grads, flags
+        return total.detach(), grads, None, flags
 
 
 def _affine(gathered: torch.Tensor, shift, mult, exp: bool, linear=None) -> torch.Tensor:
@@ -309,28 +292,6 @@ def _affine(gathered: torch.Tensor, shift, mult, exp: bool, linear=None) -> torc
     if linear is not None:
         gathered = gathered + linear
     return gathered.exp() if exp else gathered
-
-
-class _GatherSiteFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, site: SiteRecord, holder: dict, g0: float, *inputs):  # type: ignore[override]
-        params = inputs[:-2]   # (then the value and the mask)
-        total, grads, flags = site.gather.run(params, g0)
-        holder["flags"] = flags
-        ctx.grads = grads
-        ctx.g0 = g0
-        return total
-
-    @staticmethod
-    def backward(ctx, g):  # type: ignore[override]
-        g = g.contiguous()
-        for grad in ctx.grads:
-            if grad is not None:
-                K, M = grad.shape[0], grad[0].numel()
-                nat.check(nat.lib().mi_scale_rows(grad.data_ptr(), M, 1, K, M, g.data_ptr(),
-                                                  ctx.g0, nat.stream_handle(g.device)),
-                          "mi_scale_rows")
-        return (None, None, None, *ctx.grads, None, None)
 
 
 def plan_gather(site: SiteRecord, K: int, device: torch.device):
@@ -435,7 +396,7 @@ def plan_gather(site: SiteRecord, K: int, device: torch.device):
         mask = None
         if site.mask is not None:
             mask = site.mask.to(device).bool().expand(shape).reshape(-1)
-        site.gather = _GatherLauncher(site, K, device, roles, plan[0], plan[1], G, value, mask)
+        site.launcher = _GatherLauncher(site, K, device, roles, plan[0], plan[1], G, value, mask)
         return site, tuple(params), value, mask
     if ok_index and out_of_range(index, G):
         # (torch's own gather would raise this on the host and fail an assertion on the device)

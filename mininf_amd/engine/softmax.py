@@ -2,14 +2,15 @@
 Softmax regression sites: Categorical(logits = X @ Theta) with a per-particle matrix Theta
 [K, P, C], fused (``mi_softmax_linear_forward``; the model's matmul was deferred by
 :mod:`mininf_amd.linear`). Such a site is planned as a row site -- an entry (site, (Theta,), labels,
-mask) of the planner's categorical list whose record carries its launcher (``site.softmax``) -- so
-the ELBO plan, ``log_joint`` and ``LogLikelihoodLoss`` take it like a Categorical site: its
-speculative gradient is dense in Theta, and it declines absorption like every row site.
+mask) of the planner's categorical list whose record carries its launcher (``site.launcher``, run
+by ``engine._rows._run_row_site`` under the row sites' one contract) -- so the ELBO plan,
+``log_joint`` and ``LogLikelihoodLoss`` take it like a Categorical site: its speculative gradient
+is dense in Theta, and it declines absorption like every row site.
 """
 from __future__ import annotations
 
 import ctypes
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 
@@ -18,7 +19,7 @@ from .. import data
 from ..linear import put_back
 from ..particles import SiteRecord
 from ._operands import _collapse, _to_device
-from ._rows import _run_categorical
+from ._rows import _buffers, _run_categorical
 
 
 class _SoftmaxLauncher:
@@ -58,21 +59,20 @@ class _SoftmaxLauncher:
         L.site_scale = self.site.scale
         return L
 
-    def run(self, theta: torch.Tensor, g0: float, need: bool,
-            flags: Optional[torch.Tensor] = None):
-        """(total [K], speculative dtheta [K, P, C] or None, flags [1])."""
+    def run(self, params: Tuple[torch.Tensor], g0: float, flags: Optional[torch.Tensor] = None):
+        """(total [K], (speculative dtheta [K, P, C] -- None where Theta needs none --,), no
+        dvalue, flags [1]) for ``params`` = (Theta,)."""
+        theta, = params
+        need = theta.requires_grad
         device = self.device
         L = self.describe(theta, g0)
-        if flags is None:
-            flags = torch.empty(1, dtype=torch.int32, device=device)
-        else:
+        if flags is not None:
             L.options |= nat.GROUP_FLAGS_ZEROED
         size = ctypes.c_size_t()
         lib = nat.lib()
         nat.check(lib.mi_softmax_linear_workspace_bytes(ctypes.byref(L), ctypes.byref(size)),
                   "mi_softmax_linear_workspace_bytes")
-        workspace = torch.empty(max(1, size.value), dtype=torch.uint8, device=device)
-        total = torch.empty(self.K, dtype=torch.float32, device=device)
+        workspace, total, flags = _buffers(size.value, self.K, device, flags)
         dtheta = torch.empty(tuple(theta.shape), dtype=torch.float32, device=device) if need else None
         code = lib.mi_softmax_linear_forward(
             ctypes.byref(L), workspace.data_ptr(), size.value, total.data_ptr(), nat.ptr(dtheta),
@@ -80,10 +80,11 @@ class _SoftmaxLauncher:
         if code == nat.MI_EUNSUPPORTED:
             return self._materialised(theta, g0, need, flags)
         nat.check(code, "mi_softmax_linear_forward")
-        return total, dtheta, flags
+        return total, (dtheta,), None, flags
 
     def _materialised(self, theta: torch.Tensor, g0: float, need: bool, flags: torch.Tensor):
-        """The launch the library declined, as the row site on the materialised logits."""
+        """The launch the library declined, as the row site on the materialised logits: what
+        :meth:`run` returns."""
         X, value = self.X_src, self.value_src
         if self.batch is not None:
             rows = self.batch.rows.long()
@@ -96,29 +97,7 @@ class _SoftmaxLauncher:
             logits = torch.matmul(X, theta)
             total, dlogits, flags = _run_categorical(self.site, g0, logits, value, mask, need, flags)
             dtheta = torch.matmul(X.t(), dlogits) if need else None
-        return total, dtheta, flags
-
-
-class _SoftmaxLinearFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, site: SiteRecord, holder: dict, g0: float, theta: torch.Tensor,
-                value: torch.Tensor, mask: Optional[torch.Tensor]):  # type: ignore[override]
-        total, dtheta, flags = site.softmax.run(theta, g0, theta.requires_grad)
-        holder["flags"] = flags
-        ctx.dtheta = dtheta
-        ctx.g0 = g0
-        return total
-
-    @staticmethod
-    def backward(ctx, g):  # type: ignore[override]
-        dtheta = ctx.dtheta
-        if dtheta is None:
-            return None, None, None, None, None, None
-        K, M = dtheta.shape[0], dtheta[0].numel()
-        g = g.contiguous()
-        nat.check(nat.lib().mi_scale_rows(dtheta.data_ptr(), M, 1, K, M, g.data_ptr(), ctx.g0,
-                                          nat.stream_handle(g.device)), "mi_scale_rows")
-        return None, None, None, dtheta, None, None
+        return total, (dtheta,), None, flags
 
 
 def plan_softmax(site: SiteRecord, K: int, device: torch.device):
@@ -154,7 +133,7 @@ def plan_softmax(site: SiteRecord, K: int, device: torch.device):
             launcher.value_src = xb[0].loader.columns[vb[1]]
             if launcher.value_src.dtype != value.dtype:
                 launcher.batch, launcher.X_src, launcher.value_src = None, X, value
-        site.softmax = launcher
+        site.launcher = launcher
         return site, (theta,), value, mask
     put_back(site, K)
     return None

@@ -166,7 +166,7 @@ def _release_graph_refs(joints: list) -> None:
                 site.linear_theta = None
                 site.linear_X = None
                 site.gather_roles = None
-                site.gather = None
+                site.launcher = None
 
 
 def _check_warmup(collector: list) -> int:

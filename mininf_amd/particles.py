@@ -115,7 +115,6 @@ class SiteRecord:
     linear_theta_index: int = -1
     linear_theta: Optional[torch.Tensor] = None
     linear_role: int = 0      # the role that is the deferred predictor (Binomial families: 1)
-    softmax: Any = None       # engine: the mi_softmax_linear launcher of a Categorical on X @ Theta
     linear_link: str = ""     # "identity", "exp" (a Poisson rate: the log link) or, for a
                               # Categorical's logits over a [P, C] theta, "log_softmax"
     order: int = 0   # position of the sample statement in the model (errors raise in this order)
@@ -124,7 +123,9 @@ class SiteRecord:
     # mininf_amd.linear): per parameter role None or a GatherRole; after tracing its table is
     # [K, G] and its tensor terms are [K].
     gather_roles: Optional[List[Optional["GatherRole"]]] = None
-    gather: Any = None        # engine: the mi_gather_site launcher
+    # engine: the launcher of a row site planned on a deferred predictor (engine.softmax's for a
+    # Categorical on X @ Theta, engine.gather's for a group-indexed site), set when it is accepted
+    launcher: Any = None
 
 
 @dataclasses.dataclass

@@ -128,8 +128,8 @@ def test_fused_step_equals_the_materialised_one(problem, device, minibatch, monk
     loss, grads, traces, spies = elbo_step(problem, device, minibatch)
     assert traces and all(t.fallback == [] for t in traces)
     sites = [s for t in traces for s in t.sites if s.name == "y"]
-    assert sites and all(s.softmax is not None for s in sites)
-    assert all((s.softmax.batch is not None) == minibatch for s in sites)
+    assert sites and all(s.launcher is not None for s in sites)
+    assert all((s.launcher.batch is not None) == minibatch for s in sites)
     assert spies.matmuls == 0 and spies.categoricals == 0, (spies.matmuls, spies.categoricals)
     monkeypatch.setenv("MININF_AMD_DEFER_MATMUL", "0")
     ref_loss, ref_grads, _, ref_spies = elbo_step(problem, device, minibatch)
