@@ -201,10 +201,8 @@ def plan_absorption(factors: List[EntropyFactor], samples: Optional[Dict[str, to
 def entropy_factors(approximation) -> Tuple[List[EntropyFactor], list]:
     """
     Split a factorised guide into factors whose entropy the ELBO kernels evaluate (Normal, Beta,
-    Gamma) and the rest (whose entropy torch.distributions evaluates, or -- a native Dirichlet
-    factor, guide.native_dirichlet -- mi_dirichlet_entropy, or -- a native one-noise-word factor,
-    guide.native_elementwise -- mi_elementwise_entropy, or -- a native LowRankMultivariateNormal
-    factor, guide.native_lowrank -- mi_lowrank_entropy, all called by the loss). With a factor in
+    Gamma) and the rest (whose entropy the loss evaluates by guide.entropy: the own kernel of the
+    factor's family in guide.FAMILIES where it has one, else torch.distributions). With a factor in
     the rest the loss is no longer the fused node alone, so its gradients take autograd, never the
     direct-to-leaf paths.
     """

@@ -174,12 +174,9 @@ class _ElboPlan:
                 d.dgrad = nat.ptr(plan.side_dgrad if plan.side_dgrad is not None
                                   else plan.drawn.dgrad)
             else:
-                d.eps = nat.ptr(cfg.noise)
-                d.seed, d.step = guide._philox_key(cfg)
-                d.step_device = nat.ptr(guide.backward_step(cfg))   # read by the ELBO backward
-                d.stream_id = cfg.stream_id
-                d.particle_offset = cfg.particle_offset
-                d.element_offset = cfg.element_offset
+                # (the step word the ELBO backward reads)
+                d.seed, d.step, d.step_device, d.stream_id, d.particle_offset, d.element_offset, \
+                    d.eps = guide.philox_key(cfg, backward=True, element=True)
             d.num_sources = len(plan.uses)
             for s, (kind, li, oi) in enumerate(plan.uses):
                 src = d.source[s]
@@ -424,14 +421,10 @@ class _ElboPlan:
         no draw launch); deferred_reductions: site
         reductions finished by the ELBO forward; final_grads: the forward wrote the guide
         gradients (no backward launch for loss.backward()); optimizer_step: the Adam step ran in the held launch's last block (no launch of its own);
-        mvn_draws: MultivariateNormal guide factors drawn by the native sampler (mi_mvn_rsample);
-        dirichlet_draws: Dirichlet guide factors drawn by the native sampler (mi_dirichlet_rsample);
-        lowrank_draws: LowRankMultivariateNormal guide factors drawn by the native sampler
-        (mi_lowrank_rsample); elementwise_draws: Exponential, Laplace, Cauchy, HalfCauchy,
-        HalfNormal and LogNormal guide factors drawn by the native sampler
-        (mi_elementwise_rsample); lowrank_entropies: LowRankMultivariateNormal guide factors whose
+        ``<family>_draws``: guide factors drawn by the native sampler of each family of
+        guide.FAMILIES, and lowrank_entropies: LowRankMultivariateNormal guide factors whose
         entropy and its gradient the native kernel evaluated (mi_lowrank_entropy, called by the
-        loss after this plan ran); gathered_sites: sites on the model's own ``alpha[group]`` that
+        loss after this plan ran), as guide.counts() reports them; gathered_sites: sites on the model's own ``alpha[group]`` that
         this evaluation ran on a gather kernel (no [K, N] gather, no scatter-add);
         gathered_linear_sites: those of them with fixed effects, ``alpha[group] + X @ theta``, on
         mi_gather_linear_forward (no [K, N] product either); gathered_slope_sites: those of the
@@ -451,11 +444,8 @@ class _ElboPlan:
             "particle_sums": getattr(self, "ksum_count", 0),
             "final_grads": int(getattr(self, "final", None) is not None),
             "optimizer_step": 0,   # set when the optimizer step joins the held launch
-            "mvn_draws": guide.mvn_draws(),
-            "dirichlet_draws": guide.dirichlet_draws(),
-            "lowrank_draws": guide.lowrank_draws(),
-            "elementwise_draws": guide.elementwise_draws(),
-            "lowrank_entropies": 0,   # set by the loss, which evaluates the rest's entropies
+            # (lowrank_entropies: refreshed by the loss, which evaluates the rest's entropies)
+            **guide.counts(),
             "gathered_sites": len(gathered),
             "gathered_linear_sites": sum(launcher.linear for launcher in gathered),
             "gathered_slope_sites": sum(launcher.slopes for launcher in gathered),

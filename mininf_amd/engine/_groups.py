@@ -162,7 +162,6 @@ class _GroupLauncher:
                 desc.grad_mode = mode
                 dw = group.draw
                 dw.operand = index + 1
-                dw.stream_id = d.cfg.stream_id
                 dw.loc, dw.loc_stride = d.loc.data_ptr(), d.loc_s
                 dw.scale, dw.scale_stride = d.scale.data_ptr(), d.scale_s
                 source = guide.exp_source(d.scale) if fuse_exp else None
@@ -172,10 +171,9 @@ class _GroupLauncher:
                     self.exp_pending, dw.scale_exp = source
                 elif not query:
                     guide.fill_exp(d.scale)   # a deferred transform runs before the kernel reads it
-                dw.seed, dw.step = guide._philox_key(d.cfg)
-                dw.step_device = nat.ptr(d.cfg.step_device)
-                dw.particle_offset = d.cfg.particle_offset
-                dw.element_offset = d.cfg.element_offset
+                # (a lazy draw has no injected noise)
+                dw.seed, dw.step, dw.step_device, dw.stream_id, dw.particle_offset, \
+                    dw.element_offset, _ = guide.philox_key(d.cfg, element=True)
                 if mode == nat.GRAD_DENSE and self.draw_partials:
                     group.options |= nat.GROUP_DRAW_PARTIALS
                 elif mode == nat.GRAD_DENSE and query:

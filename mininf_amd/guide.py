@@ -2,30 +2,27 @@
 Reparameterised guide sampling over K particles (replaces ``FactorizedDistribution.rsample``,
 reference ``mininf/nn.py:133-145``, with ONE draw per call at ``nn.py:217``).
 
-Normal, Beta, Gamma, Dirichlet, full-covariance MultivariateNormal, LowRankMultivariateNormal,
-Exponential, Laplace, Cauchy, HalfCauchy, HalfNormal and LogNormal
-factors are drawn by HIP kernels from a counter-based Philox generator keyed by (seed, step, factor index, global particle
-index, element), so that K particles split over W GPUs draw exactly the union of what one GPU would
-draw. Other families (and a batched, float64, host-resident or D > MI_MVN_MAX_N
-MultivariateNormal; a subclassed, float64, host-resident or C > MI_DIRICHLET_MAX_C Dirichlet; a
-batched, subclassed, float64, host-resident or R > MI_LOWRANK_MAX_R LowRankMultivariateNormal; a
-subclassed, float64 or host-resident factor of the last six) use
-their own ``torch.distributions`` ``rsample`` on the device.
+Normal, Beta and Gamma factors, and the families of :data:`FAMILIES` (a record each: what the
+native sampler accepts, how it is called, its entropy), are drawn by HIP kernels from a
+counter-based Philox generator keyed by (seed, step, factor index, global particle index, element),
+so that K particles split over W GPUs draw exactly the union of what one GPU would draw. Every
+other factor, and one a record's ``accepts`` declines, uses its own ``torch.distributions``
+``rsample`` on the device.
 
 Parity mode: ``noise[name]`` injects host-drawn standard normals (Normal factors, [K, *shape];
 MultivariateNormal factors, [K, D]; LowRankMultivariateNormal factors, [K, D + R]: eps_D, then
 eps_W), the draws themselves (Beta factors) or the standard Gamma
 draws g with x = g / rate (Gamma factors) or x = g / sum(g) (Dirichlet factors, [K, *batch, C]),
 exactly as the oracle's sample-injection protocol does, or the base noise
-[K, *shape] of the last six families: uniforms in (0, 1), standard normals for HalfNormal and
-LogNormal.
+[K, *shape] of the one-noise-word families: uniforms in (0, 1), standard normals for HalfNormal
+and LogNormal.
 """
 from __future__ import annotations
 
 import collections
 import ctypes
 import dataclasses
-from typing import Dict, Optional, Tuple
+from typing import Callable, Dict, Optional, Tuple
 
 import torch
 from torch.distributions import Beta, Cauchy, Dirichlet, Distribution, Exponential, Gamma, \
@@ -84,8 +81,17 @@ def _flat_param(t: torch.Tensor, N: int) -> Tuple[torch.Tensor, int]:
     return flat, flat.stride(0)
 
 
-def _philox_key(cfg: DrawConfig) -> Tuple[int, int]:
-    return cfg.seed & 0xFFFFFFFFFFFFFFFF, cfg.step & 0xFFFFFFFFFFFFFFFF
+def philox_key(cfg: DrawConfig, backward: bool = False, element: bool = False) -> tuple:
+    """
+    The Philox key arguments of a native sampler call, in the order of the C ABI: seed, step, the
+    device step word (the forward's; with ``backward``, the one its backward regenerates the noise
+    from), stream id, particle offset, with ``element`` the element offset (the Normal entry
+    points alone take it), injected noise.
+    """
+    word = backward_step(cfg) if backward else cfg.step_device
+    offsets = (cfg.particle_offset, cfg.element_offset) if element else (cfg.particle_offset,)
+    return (cfg.seed & 0xFFFFFFFFFFFFFFFF, cfg.step & 0xFFFFFFFFFFFFFFFF, nat.ptr(word),
+            cfg.stream_id, *offsets, nat.ptr(cfg.noise))
 
 
 def _workspace(query: str, *dims: int, device: torch.device) -> Tuple[torch.Tensor, int]:
@@ -108,8 +114,8 @@ def _inject(cfg: DrawConfig, device: torch.device, *shape: int) -> None:
             .contiguous()
 
 
-# factors the native "mvn", "dirichlet", "lowrank" and "elementwise" samplers drew in the last draw_all
-# (EvidenceLowerBoundLoss.last_fusions["<family>_draws"])
+# factors each family of FAMILIES drew in the last draw_all, by its counter, and under
+# "lowrank_entropy" those whose entropy mi_lowrank_entropy evaluated since (counts())
 _DRAWS: "collections.Counter[str]" = collections.Counter()
 
 
@@ -142,11 +148,9 @@ class _NormalRsampleFn(torch.autograd.Function):
                                      device=device)
         dloc = torch.empty(N, dtype=torch.float32, device=device)
         deps_scale = torch.empty(N, dtype=torch.float32, device=device)
-        seed, step = _philox_key(cfg)
         nat.check(nat.lib().mi_normal_rsample_backward(
-            dz.data_ptr(), dz.stride(0), dz.stride(1), K, N, seed, step,
-            nat.ptr(backward_step(cfg)), cfg.stream_id, cfg.particle_offset, cfg.element_offset,
-            nat.ptr(cfg.noise), workspace.data_ptr(), size,
+            dz.data_ptr(), dz.stride(0), dz.stride(1), K, N,
+            *philox_key(cfg, backward=True, element=True), workspace.data_ptr(), size,
             dloc.data_ptr(), deps_scale.data_ptr(), nat.stream_handle(device)),
             "mi_normal_rsample_backward")
         # dz/dscale = eps: the kernel returns sum_k dz * eps directly.
@@ -320,21 +324,18 @@ class _BetaRsampleFn(torch.autograd.Function):
         N = conc.shape[0]
         K = cfg.K
         x = torch.empty((K, N), dtype=torch.float32, device=conc.device)
-        seed, step = _philox_key(cfg)
         base = conc.data_ptr()
         pending = pending_exp(conc)
         if pending is not None:   # the guide's exp transform and the draw in one launch
             u1, u0 = pending.u1.reshape(-1), pending.u0.reshape(-1)
             nat.check(nat.lib().mi_beta_rsample_exp(
                 u1.data_ptr(), u1.stride(0) if u1.numel() > 1 else 0, u0.data_ptr(),
-                u0.stride(0) if u0.numel() > 1 else 0, base, K, N, seed, step,
-                nat.ptr(cfg.step_device), cfg.stream_id, cfg.particle_offset, nat.ptr(cfg.noise),
+                u0.stride(0) if u0.numel() > 1 else 0, base, K, N, *philox_key(cfg),
                 x.data_ptr(), nat.stream_handle(conc.device)), "mi_beta_rsample_exp")
             pending.filled = True
         else:
             nat.check(nat.lib().mi_beta_rsample(
-                base, 2, base + 4, 2, K, N, seed, step, nat.ptr(cfg.step_device), cfg.stream_id,
-                cfg.particle_offset, nat.ptr(cfg.noise), x.data_ptr(),
+                base, 2, base + 4, 2, K, N, *philox_key(cfg), x.data_ptr(),
                 nat.stream_handle(conc.device)), "mi_beta_rsample")
         ctx.save_for_backward(x, conc)
         ctx.K, ctx.N = K, N
@@ -363,49 +364,127 @@ def gamma_params(distribution: Gamma, N: int) -> Tuple[torch.Tensor, int, torch.
     return conc, conc_s, rate, rate_s
 
 
-class _GammaRsampleFn(torch.autograd.Function):
+@dataclasses.dataclass(frozen=True)
+class _Sampler:
     """
-    Gamma.rsample (gamma.py:80-88) over K particles: mi_gamma_rsample, and its backward through
-    torch._standard_gamma_grad restated in fp64 (mi_gamma_rsample_backward). ``cfg.noise`` injects
-    the standard Gamma draws g (x = g / rate), the oracle's protocol for Gamma factors.
+    How :class:`_RsampleFn` calls one family's entry points ``<stem>``, ``<stem>_backward`` and
+    ``<stem>_backward_workspace_bytes``. With ``inputs`` the family's arguments of
+    ``_RsampleFn.apply`` (tensors go by address), the forward is
+    ``<stem>(*inputs, K, *sizes, *key, [g,] out, stream)`` and the backward
+    ``<stem>_backward(*reads, K, *sizes, [*key,] workspace, bytes, *gradients, stream)``.
     """
+    stem: str
+    # positions among the inputs of the float32 parameters: one gradient each, of the parameter's
+    # shape; the first has the shape of one particle's draw
+    params: Tuple[int, ...]
+    saves: Tuple[int, ...]   # positions of the inputs the backward reads
+    sizes: Callable          # (*inputs) -> the sizes that follow K in the three entry points
+    # (dz and its strides, the inputs with only the saved tensors' addresses, the saved draws'
+    # address) -> the backward's arguments before K
+    reads: Callable
+    # The backward of a family without saved draws regenerates the noise from the key. "out": it
+    # reads the draws instead; "standard": the standard draws g, which the forward writes as well.
+    draws: Optional[str] = None
+    after_gradient: Tuple[int, ...] = ()   # follows every gradient address (Gamma: its stride)
+    # a gradient nobody needs is null, and nothing is launched when none is needed; the other
+    # families always write all of theirs
+    optional: bool = False
+
+
+class _RsampleFn(torch.autograd.Function):
+    """K reparameterised draws of one guide factor through its family's :class:`_Sampler`."""
     @staticmethod
-    def forward(ctx, cfg: DrawConfig, conc: torch.Tensor, conc_s: int, rate: torch.Tensor,
-                rate_s: int):  # type: ignore[override]
-        N, K = conc.shape[0], cfg.K
-        # a deferred exp transform of the guide's parameters runs before the sampler reads them
-        # (no validation read has forced it when torch's argument validation is off, e.g. in a
-        # captured step)
-        fill_exp(conc)
-        fill_exp(rate)
-        x = torch.empty((K, N), dtype=torch.float32, device=conc.device)
-        g = torch.empty((K, N), dtype=torch.float32, device=conc.device)
-        seed, step = _philox_key(cfg)
-        nat.check(nat.lib().mi_gamma_rsample(
-            conc.data_ptr(), conc_s, rate.data_ptr(), rate_s, K, N, seed, step,
-            nat.ptr(cfg.step_device), cfg.stream_id, cfg.particle_offset, nat.ptr(cfg.noise),
-            g.data_ptr(), x.data_ptr(), nat.stream_handle(conc.device)), "mi_gamma_rsample")
-        ctx.save_for_backward(g, conc, rate)
-        ctx.strides = (conc_s, rate_s)
-        ctx.K, ctx.N = K, N
-        return x
+    def forward(ctx, family: _Sampler, cfg: DrawConfig, *inputs):  # type: ignore[override]
+        K, first = cfg.K, inputs[family.params[0]]
+        sizes = tuple(family.sizes(*inputs))
+        out = torch.empty((K,) + tuple(first.shape), dtype=torch.float32, device=first.device)
+        g = torch.empty_like(out) if family.draws == "standard" else None
+        nat.check(getattr(nat.lib(), family.stem)(
+            *(nat.ptr(x) if isinstance(x, torch.Tensor) else x for x in inputs), K, *sizes,
+            *philox_key(cfg), *(() if g is None else (g.data_ptr(),)), out.data_ptr(),
+            nat.stream_handle(first.device)), family.stem)
+        ctx.family, ctx.cfg, ctx.sizes = family, cfg, sizes
+        ctx.shapes = [tuple(inputs[i].shape) if inputs[i] is not None else None
+                      for i in family.params]
+        ctx.args = [None if isinstance(x, torch.Tensor) else x for x in inputs]
+        ctx.save_for_backward(*(inputs[i] for i in family.saves),
+                              *((g,) if g is not None else (out,) if family.draws else ()))
+        return out
 
     @staticmethod
-    def backward(ctx, dx: torch.Tensor):  # type: ignore[override]
-        g, conc, rate = ctx.saved_tensors
-        conc_s, rate_s = ctx.strides
-        K, N = ctx.K, ctx.N
-        device = dx.device
-        workspace, size = _workspace("mi_gamma_rsample_backward_workspace_bytes", K, N,
+    def backward(ctx, dz: torch.Tensor):  # type: ignore[override]
+        family, cfg, K = ctx.family, ctx.cfg, ctx.cfg.K
+        grads = [None] * (2 + len(ctx.args))
+        need = [shape is not None and (not family.optional or ctx.needs_input_grad[2 + i])
+                for i, shape in zip(family.params, ctx.shapes)]
+        if not any(need):
+            return tuple(grads)
+        device, dz = dz.device, _float32(dz)
+        inputs, saved = list(ctx.args), ctx.saved_tensors
+        for i, tensor in zip(family.saves, saved):
+            inputs[i] = nat.ptr(tensor)
+        workspace, size = _workspace(family.stem + "_backward_workspace_bytes", K, *ctx.sizes,
                                      device=device)
-        dconc = torch.empty(N, dtype=torch.float32, device=device)
-        drate = torch.empty(N, dtype=torch.float32, device=device)
-        nat.check(nat.lib().mi_gamma_rsample_backward(
-            dx.data_ptr(), dx.stride(0), dx.stride(1), g.data_ptr(), conc.data_ptr(), conc_s,
-            rate.data_ptr(), rate_s, K, N, workspace.data_ptr(), size, dconc.data_ptr(), 1,
-            drate.data_ptr(), 1, nat.stream_handle(device)), "mi_gamma_rsample_backward")
-        # per element; a broadcast parameter's expand backward sums them
-        return None, dconc, None, drate, None
+        pointers = []
+        for i, shape, wanted in zip(family.params, ctx.shapes, need):
+            if wanted:
+                grads[2 + i] = torch.empty(shape, dtype=torch.float32, device=device)
+            pointers += [nat.ptr(grads[2 + i]), *family.after_gradient]
+        nat.check(getattr(nat.lib(), family.stem + "_backward")(
+            *family.reads((dz.data_ptr(), *dz.stride()), inputs,
+                          saved[-1].data_ptr() if family.draws else None), K, *ctx.sizes,
+            *(() if family.draws else philox_key(cfg, backward=True)), workspace.data_ptr(), size,
+            *pointers, nat.stream_handle(device)), family.stem + "_backward")
+        # (per element: a broadcast parameter's expand backward sums them)
+        return tuple(grads)
+
+
+# Gamma.rsample (gamma.py:80-88): inputs (concentration, stride, rate, stride), as gamma_params
+# gives them. The backward is torch._standard_gamma_grad restated in fp64. ``cfg.noise`` injects
+# the standard Gamma draws g (x = g / rate), the oracle's protocol for Gamma factors.
+_GAMMA = _Sampler("mi_gamma_rsample", params=(0, 2), saves=(0, 2), draws="standard",
+                  after_gradient=(1,), sizes=lambda conc, *_: conc.shape,
+                  reads=lambda dx, inputs, g: (*dx, g, *inputs))
+# MultivariateNormal.rsample (multivariate_normal.py:247-250): inputs (loc [D], scale_tril [D, D]);
+# z = loc + eps @ scale_tril^T with the Philox eps of a Normal factor of D elements. ``cfg.noise``
+# injects eps [K, D], as for a Normal factor.
+_MVN = _Sampler("mi_mvn_rsample", params=(0, 1), saves=(), sizes=lambda loc, tril: loc.shape,
+                reads=lambda dz, inputs, _: dz)
+# LowRankMultivariateNormal.rsample (lowrank_multivariate_normal.py:214-223): inputs (loc [D],
+# cov_factor [D, R], cov_diag [D]); z = loc + eps_W @ cov_factor^T + sqrt(cov_diag) * eps_D, both
+# sets of normals from the factor's one Normal stream (eps_D: elements [0, D); eps_W: elements
+# [Dpad, Dpad + R)). ``cfg.noise`` injects [K, D + R]: eps_D, then eps_W.
+_LOWRANK = _Sampler("mi_lowrank_rsample", params=(0, 1, 2), saves=(2,),
+                    sizes=lambda loc, cov_factor, cov_diag: cov_factor.shape,
+                    reads=lambda dz, inputs, _: (*dz, inputs[2]))
+# Dirichlet.rsample (dirichlet.py:85-88): input (concentration [N, C]); normalised standard Gamma
+# draws, and _Dirichlet_backward (dirichlet.py:17-20) in fp64 from the saved draws. ``cfg.noise``
+# injects the standard Gamma draws g [K, N, C], as for a Gamma factor.
+_DIRICHLET = _Sampler("mi_dirichlet_rsample", params=(0,), saves=(0,), draws="out",
+                      sizes=lambda conc: conc.shape,
+                      reads=lambda dx, inputs, x: (*dx, x, *inputs))
+# The one-noise-word families: inputs (MI_PRED_* code, a [N], stride, b [N] or None, stride), as
+# _elementwise_params gives them. ``cfg.noise`` injects the base noise [K, N]: uniforms, or
+# standard normals for HalfNormal and LogNormal.
+_ELEMENTWISE_SAMPLER = _Sampler("mi_elementwise_rsample", params=(1, 3), saves=(1, 3),
+                                optional=True, sizes=lambda code, a, *_: a.shape,
+                                reads=lambda dz, inputs, _: (inputs[0], *dz, *inputs[1:]))
+
+
+class _EntropyFn(torch.autograd.Function):
+    """
+    A factor's summed entropy and its gradients in one launch: ``launch(needs, *inputs)`` (``needs``
+    this node's needs_input_grad of the inputs) returns the 0-d value and one gradient per input,
+    None where there is none. The backward scales the stored gradients.
+    """
+    @staticmethod
+    def forward(ctx, launch: Callable, *inputs):  # type: ignore[override]
+        out, ctx.grads = launch(ctx.needs_input_grad[1:], *inputs)
+        return out
+
+    @staticmethod
+    def backward(ctx, g: torch.Tensor):  # type: ignore[override]
+        return (None, *(None if grad is None else grad * g for grad in ctx.grads))
 
 
 def native_mvn(distribution) -> bool:
@@ -421,47 +500,17 @@ def native_mvn(distribution) -> bool:
         1 <= int(distribution.event_shape[0]) <= nat.MVN_MAX_N
 
 
-class _MvnRsampleFn(torch.autograd.Function):
-    """
-    MultivariateNormal.rsample (multivariate_normal.py:247-250) over K particles:
-    z = loc + eps @ scale_tril^T by mi_mvn_rsample, with the Philox eps of a Normal factor of D
-    elements; the backward regenerates eps (mi_mvn_rsample_backward). ``cfg.noise`` injects eps
-    [K, D], as for a Normal factor.
-    """
-    @staticmethod
-    def forward(ctx, cfg: DrawConfig, loc: torch.Tensor,
-                scale_tril: torch.Tensor):  # type: ignore[override]
-        D, K = loc.shape[0], cfg.K
-        z = torch.empty((K, D), dtype=torch.float32, device=loc.device)
-        seed, step = _philox_key(cfg)
-        nat.check(nat.lib().mi_mvn_rsample(
-            loc.data_ptr(), scale_tril.data_ptr(), K, D, seed, step, nat.ptr(cfg.step_device),
-            cfg.stream_id, cfg.particle_offset, nat.ptr(cfg.noise), z.data_ptr(),
-            nat.stream_handle(loc.device)), "mi_mvn_rsample")
-        ctx.cfg = cfg
-        ctx.D = D
-        return z
-
-    @staticmethod
-    def backward(ctx, dz: torch.Tensor):  # type: ignore[override]
-        cfg: DrawConfig = ctx.cfg
-        D, K = ctx.D, cfg.K
-        device, dz = dz.device, _float32(dz)
-        workspace, size = _workspace("mi_mvn_rsample_backward_workspace_bytes", K, D,
-                                     device=device)
-        dloc = torch.empty(D, dtype=torch.float32, device=device)
-        dtril = torch.empty((D, D), dtype=torch.float32, device=device)
-        seed, step = _philox_key(cfg)
-        nat.check(nat.lib().mi_mvn_rsample_backward(
-            dz.data_ptr(), dz.stride(0), dz.stride(1), K, D, seed, step,
-            nat.ptr(backward_step(cfg)), cfg.stream_id, cfg.particle_offset, nat.ptr(cfg.noise),
-            workspace.data_ptr(), size, dloc.data_ptr(), dtril.data_ptr(),
-            nat.stream_handle(device)), "mi_mvn_rsample_backward")
-        return None, dloc, dtril
-
-
-def mvn_draws() -> int:
-    return _DRAWS["mvn"]
+def _mvn_inputs(distribution: MultivariateNormal):
+    """(:data:`_MVN`'s inputs, the shape of the injected noise after K, that of the result) of a
+    :func:`native_mvn` factor."""
+    # the public properties: scale_tril carries the autograd of a covariance_matrix /
+    # precision_matrix parameterisation
+    D = int(distribution.event_shape[0])
+    loc = distribution.loc.reshape(D).contiguous()
+    scale_tril = distribution.scale_tril.reshape(D, D)
+    if scale_tril.dtype != torch.float32:
+        raise nat.NativeError(f"guide parameters must be float32, got {scale_tril.dtype}")
+    return (loc, scale_tril.contiguous()), (D,), (D,)   # eps, [K, D]
 
 
 def native_lowrank(distribution) -> bool:
@@ -482,83 +531,39 @@ def native_lowrank(distribution) -> bool:
         1 <= int(distribution.event_shape[0]) <= nat.LOWRANK_MAX_D
 
 
-class _LowRankRsampleFn(torch.autograd.Function):
-    """
-    LowRankMultivariateNormal.rsample (lowrank_multivariate_normal.py:214-223) over K particles:
-    z = loc + eps_W @ cov_factor^T + sqrt(cov_diag) * eps_D by mi_lowrank_rsample, both sets of
-    normals from the factor's one Normal stream (eps_D: elements [0, D); eps_W: elements
-    [Dpad, Dpad + R)); the backward regenerates them (mi_lowrank_rsample_backward).
-    ``cfg.noise`` injects [K, D + R]: eps_D, then eps_W.
-    """
-    @staticmethod
-    def forward(ctx, cfg: DrawConfig, loc: torch.Tensor, cov_factor: torch.Tensor,
-                cov_diag: torch.Tensor):  # type: ignore[override]
-        (D, R), K = cov_factor.shape, cfg.K
-        z = torch.empty((K, D), dtype=torch.float32, device=loc.device)
-        seed, step = _philox_key(cfg)
-        nat.check(nat.lib().mi_lowrank_rsample(
-            loc.data_ptr(), cov_factor.data_ptr(), cov_diag.data_ptr(), K, D, R, seed, step,
-            nat.ptr(cfg.step_device), cfg.stream_id, cfg.particle_offset, nat.ptr(cfg.noise),
-            z.data_ptr(), nat.stream_handle(loc.device)), "mi_lowrank_rsample")
-        ctx.cfg = cfg
-        ctx.save_for_backward(cov_diag)
-        ctx.shape = (D, R)
-        return z
-
-    @staticmethod
-    def backward(ctx, dz: torch.Tensor):  # type: ignore[override]
-        cfg: DrawConfig = ctx.cfg
-        (cov_diag,) = ctx.saved_tensors
-        (D, R), K = ctx.shape, cfg.K
-        device, dz = dz.device, _float32(dz)
-        workspace, size = _workspace("mi_lowrank_rsample_backward_workspace_bytes", K, D, R,
-                                     device=device)
-        dloc = torch.empty(D, dtype=torch.float32, device=device)
-        dfactor = torch.empty((D, R), dtype=torch.float32, device=device)
-        ddiag = torch.empty(D, dtype=torch.float32, device=device)
-        seed, step = _philox_key(cfg)
-        nat.check(nat.lib().mi_lowrank_rsample_backward(
-            dz.data_ptr(), dz.stride(0), dz.stride(1), cov_diag.data_ptr(), K, D, R, seed, step,
-            nat.ptr(backward_step(cfg)), cfg.stream_id, cfg.particle_offset, nat.ptr(cfg.noise),
-            workspace.data_ptr(), size, dloc.data_ptr(), dfactor.data_ptr(),
-            ddiag.data_ptr(), nat.stream_handle(device)), "mi_lowrank_rsample_backward")
-        return None, dloc, dfactor, ddiag
+def _lowrank_inputs(distribution: LowRankMultivariateNormal):
+    """(:data:`_LOWRANK`'s inputs, the shape of the injected noise after K, that of the result) of
+    a :func:`native_lowrank` factor."""
+    # the public loc and the unbroadcast cov_factor / cov_diag (of an unbatched factor: the
+    # constructor's own arguments, which carry the autograd of the parameterisation)
+    cov_factor = distribution._unbroadcasted_cov_factor
+    cov_diag = distribution._unbroadcasted_cov_diag
+    fill_exp(cov_diag)
+    D, R = (int(n) for n in cov_factor.shape)
+    loc = distribution.loc.reshape(D).contiguous()
+    # eps_D | eps_W, [K, D + R]
+    return (loc, cov_factor.contiguous(), cov_diag.contiguous()), (D + R,), (D,)
 
 
-def lowrank_draws() -> int:
-    return _DRAWS["lowrank"]
-
-
-class _LowRankEntropyFn(torch.autograd.Function):
+def _lowrank_entropy(needs, cov_factor: torch.Tensor, cov_diag: torch.Tensor, tril: torch.Tensor):
     """
     LowRankMultivariateNormal.entropy() (lowrank_multivariate_normal.py:225-237) and its gradient
-    with respect to cov_factor and cov_diag in closed form, in one mi_lowrank_entropy call; the
-    backward scales the stored gradients. ``tril`` is the factor's _capacitance_tril, detached:
-    the closed form carries its whole dependence on the two parameters.
+    with respect to cov_factor and cov_diag in closed form, in one mi_lowrank_entropy call.
+    ``tril`` is the factor's _capacitance_tril, detached: the closed form carries its whole
+    dependence on the two parameters.
     """
-    @staticmethod
-    def forward(ctx, cov_factor: torch.Tensor, cov_diag: torch.Tensor,
-                tril: torch.Tensor):  # type: ignore[override]
-        D, R = cov_factor.shape
-        device = cov_factor.device
-        out = torch.empty((), dtype=torch.float32, device=device)
-        grads = cov_factor.requires_grad or cov_diag.requires_grad
-        dfactor = torch.empty_like(cov_factor) if grads else None
-        ddiag = torch.empty_like(cov_diag) if grads else None
-        workspace, size = _workspace("mi_lowrank_entropy_workspace_bytes", D, R, device=device)
-        nat.check(nat.lib().mi_lowrank_entropy(
-            cov_factor.data_ptr(), cov_diag.data_ptr(), tril.data_ptr(), D, R,
-            workspace.data_ptr(), size, out.data_ptr(), nat.ptr(dfactor), nat.ptr(ddiag),
-            nat.stream_handle(device)), "mi_lowrank_entropy")
-        ctx.grads = (dfactor, ddiag)
-        return out
-
-    @staticmethod
-    def backward(ctx, g: torch.Tensor):  # type: ignore[override]
-        dfactor, ddiag = ctx.grads
-        if dfactor is None:
-            return None, None, None
-        return dfactor * g, ddiag * g, None
+    D, R = cov_factor.shape
+    device = cov_factor.device
+    out = torch.empty((), dtype=torch.float32, device=device)
+    grads = cov_factor.requires_grad or cov_diag.requires_grad
+    dfactor = torch.empty_like(cov_factor) if grads else None
+    ddiag = torch.empty_like(cov_diag) if grads else None
+    workspace, size = _workspace("mi_lowrank_entropy_workspace_bytes", D, R, device=device)
+    nat.check(nat.lib().mi_lowrank_entropy(
+        cov_factor.data_ptr(), cov_diag.data_ptr(), tril.data_ptr(), D, R,
+        workspace.data_ptr(), size, out.data_ptr(), nat.ptr(dfactor), nat.ptr(ddiag),
+        nat.stream_handle(device)), "mi_lowrank_entropy")
+    return out, (dfactor, ddiag, None)
 
 
 def lowrank_entropy(distribution: LowRankMultivariateNormal) -> torch.Tensor:
@@ -569,14 +574,8 @@ def lowrank_entropy(distribution: LowRankMultivariateNormal) -> torch.Tensor:
     fill_exp(cov_diag)
     tril = distribution._capacitance_tril.detach()
     _DRAWS["lowrank_entropy"] += 1
-    return _LowRankEntropyFn.apply(cov_factor.contiguous(), cov_diag.contiguous(),
-                                   tril.contiguous())
-
-
-def lowrank_entropies() -> int:
-    """LowRankMultivariateNormal factors whose entropy mi_lowrank_entropy evaluated since the last
-    draw_all (EvidenceLowerBoundLoss.last_fusions["lowrank_entropies"])."""
-    return _DRAWS["lowrank_entropy"]
+    return _EntropyFn.apply(_lowrank_entropy, cov_factor.contiguous(), cov_diag.contiguous(),
+                            tril.contiguous())
 
 
 def native_dirichlet(distribution) -> bool:
@@ -600,66 +599,29 @@ def _dirichlet_rows(distribution: Dirichlet) -> torch.Tensor:
     return conc.reshape(max(1, int(distribution.batch_shape.numel())), C).contiguous()
 
 
-class _DirichletRsampleFn(torch.autograd.Function):
-    """
-    Dirichlet.rsample (dirichlet.py:85-88) over K particles: normalised standard Gamma draws by
-    mi_dirichlet_rsample, and _Dirichlet_backward (dirichlet.py:17-20) in fp64 from the saved
-    draws (mi_dirichlet_rsample_backward). ``cfg.noise`` injects the standard Gamma draws g
-    [K, N, C], as for a Gamma factor.
-    """
-    @staticmethod
-    def forward(ctx, cfg: DrawConfig, conc: torch.Tensor):  # type: ignore[override]
-        (N, C), K = conc.shape, cfg.K
-        x = torch.empty((K, N, C), dtype=torch.float32, device=conc.device)
-        seed, step = _philox_key(cfg)
-        nat.check(nat.lib().mi_dirichlet_rsample(
-            conc.data_ptr(), K, N, C, seed, step, nat.ptr(cfg.step_device), cfg.stream_id,
-            cfg.particle_offset, nat.ptr(cfg.noise), x.data_ptr(),
-            nat.stream_handle(conc.device)), "mi_dirichlet_rsample")
-        ctx.save_for_backward(x, conc)
-        return x
-
-    @staticmethod
-    def backward(ctx, dx: torch.Tensor):  # type: ignore[override]
-        x, conc = ctx.saved_tensors
-        K, N, C = x.shape
-        device, dx = x.device, _float32(dx)
-        workspace, size = _workspace("mi_dirichlet_rsample_backward_workspace_bytes", K, N, C,
-                                     device=device)
-        dconc = torch.empty((N, C), dtype=torch.float32, device=device)
-        nat.check(nat.lib().mi_dirichlet_rsample_backward(
-            dx.data_ptr(), dx.stride(0), dx.stride(1), dx.stride(2), x.data_ptr(), conc.data_ptr(),
-            K, N, C, workspace.data_ptr(), size, dconc.data_ptr(),
-            nat.stream_handle(device)), "mi_dirichlet_rsample_backward")
-        return None, dconc
+def _dirichlet_inputs(distribution: Dirichlet):
+    """(:data:`_DIRICHLET`'s input, the shape of the injected noise after K, that of the result) of
+    a :func:`native_dirichlet` factor."""
+    conc = _dirichlet_rows(distribution)
+    # standard draws g, [K, *batch, C]
+    return (conc,), tuple(conc.shape), tuple(distribution.batch_shape) + (int(conc.shape[1]),)
 
 
-class _DirichletEntropyFn(torch.autograd.Function):
+def _dirichlet_entropy(needs, conc: torch.Tensor):
     """Dirichlet.entropy().sum() (dirichlet.py:122-130) and its gradient in one launch
-    (mi_dirichlet_entropy); the backward scales the stored gradient."""
-    @staticmethod
-    def forward(ctx, conc: torch.Tensor):  # type: ignore[override]
-        N, C = conc.shape
-        out = torch.empty((), dtype=torch.float32, device=conc.device)
-        grad = torch.empty_like(conc) if conc.requires_grad else None
-        nat.check(nat.lib().mi_dirichlet_entropy(
-            conc.data_ptr(), N, C, out.data_ptr(), nat.ptr(grad),
-            nat.stream_handle(conc.device)), "mi_dirichlet_entropy")
-        ctx.grad = grad
-        return out
-
-    @staticmethod
-    def backward(ctx, g: torch.Tensor):  # type: ignore[override]
-        return None if ctx.grad is None else ctx.grad * g
+    (mi_dirichlet_entropy)."""
+    N, C = conc.shape
+    out = torch.empty((), dtype=torch.float32, device=conc.device)
+    grad = torch.empty_like(conc) if conc.requires_grad else None
+    nat.check(nat.lib().mi_dirichlet_entropy(
+        conc.data_ptr(), N, C, out.data_ptr(), nat.ptr(grad),
+        nat.stream_handle(conc.device)), "mi_dirichlet_entropy")
+    return out, (grad,)
 
 
 def dirichlet_entropy(distribution: Dirichlet) -> torch.Tensor:
     """The summed entropy of a :func:`native_dirichlet` guide factor (0-d, differentiable)."""
-    return _DirichletEntropyFn.apply(_dirichlet_rows(distribution))
-
-
-def dirichlet_draws() -> int:
-    return _DRAWS["dirichlet"]
+    return _EntropyFn.apply(_dirichlet_entropy, _dirichlet_rows(distribution))
 
 
 # ---- one-noise-word families -------------------------------------------------------------------
@@ -715,83 +677,78 @@ def _elementwise_params(distribution, N: int):
     return _ELEMENTWISE[type(distribution)], a, a_s, b, b_s
 
 
-class _ElementwiseRsampleFn(torch.autograd.Function):
-    """
-    rsample of the one-noise-word families over K particles by mi_elementwise_rsample; the backward
-    regenerates the noise (mi_elementwise_rsample_backward). ``cfg.noise`` injects the base noise
-    [K, N]: uniforms, or standard normals for HalfNormal and LogNormal.
-    """
-    @staticmethod
-    def forward(ctx, cfg: DrawConfig, family: int, a: torch.Tensor, a_s: int,
-                b: Optional[torch.Tensor], b_s: int):  # type: ignore[override]
-        N, K = a.shape[0], cfg.K
-        z = torch.empty((K, N), dtype=torch.float32, device=a.device)
-        seed, step = _philox_key(cfg)
-        nat.check(nat.lib().mi_elementwise_rsample(
-            family, a.data_ptr(), a_s, nat.ptr(b), b_s, K, N, seed, step,
-            nat.ptr(cfg.step_device), cfg.stream_id, cfg.particle_offset, nat.ptr(cfg.noise),
-            z.data_ptr(), nat.stream_handle(a.device)), "mi_elementwise_rsample")
-        ctx.cfg, ctx.family, ctx.strides, ctx.N = cfg, family, (a_s, b_s), N
-        ctx.save_for_backward(a, b)
-        return z
-
-    @staticmethod
-    def backward(ctx, dz: torch.Tensor):  # type: ignore[override]
-        cfg: DrawConfig = ctx.cfg
-        a, b = ctx.saved_tensors
-        (a_s, b_s), N, K = ctx.strides, ctx.N, cfg.K
-        device, dz = dz.device, _float32(dz)
-        need_a = ctx.needs_input_grad[2]
-        need_b = b is not None and ctx.needs_input_grad[4]
-        if not (need_a or need_b):
-            return None, None, None, None, None, None
-        workspace, size = _workspace("mi_elementwise_rsample_backward_workspace_bytes", K, N,
-                                     device=device)
-        da = torch.empty(N, dtype=torch.float32, device=device) if need_a else None
-        db = torch.empty(N, dtype=torch.float32, device=device) if need_b else None
-        seed, step = _philox_key(cfg)
-        nat.check(nat.lib().mi_elementwise_rsample_backward(
-            ctx.family, dz.data_ptr(), dz.stride(0), dz.stride(1), a.data_ptr(), a_s, nat.ptr(b),
-            b_s, K, N, seed, step, nat.ptr(backward_step(cfg)), cfg.stream_id,
-            cfg.particle_offset, nat.ptr(cfg.noise), workspace.data_ptr(), size, nat.ptr(da),
-            nat.ptr(db), nat.stream_handle(device)), "mi_elementwise_rsample_backward")
-        # per element; a broadcast parameter's expand backward sums them
-        return None, None, da, None, db, None
+def _elementwise_inputs(distribution):
+    """(:data:`_ELEMENTWISE_SAMPLER`'s inputs, the shape of the injected noise after K, that of the
+    result) of a :func:`native_elementwise` factor."""
+    shape = tuple(distribution.batch_shape)
+    N = max(1, int(distribution.batch_shape.numel()))
+    # base noise (uniforms or normals), [K, *shape]
+    return _elementwise_params(distribution, N), (N,), shape
 
 
-class _ElementwiseEntropyFn(torch.autograd.Function):
+def _elementwise_entropy(needs, family: int, a: torch.Tensor, a_s: int,
+                         b: Optional[torch.Tensor], b_s: int):
     """entropy().sum() of a one-noise-word factor and its gradient in one launch
-    (mi_elementwise_entropy); the backward scales the stored gradient."""
-    @staticmethod
-    def forward(ctx, family: int, a: torch.Tensor, a_s: int, b: Optional[torch.Tensor],
-                b_s: int):  # type: ignore[override]
-        N = a.shape[0]
-        out = torch.empty((), dtype=torch.float32, device=a.device)
-        # (the entropy of a Laplace or Cauchy factor does not depend on its loc)
-        da = torch.empty(N, dtype=torch.float32, device=a.device) if ctx.needs_input_grad[1] and \
-            family not in (nat.PRED_LAPLACE, nat.PRED_CAUCHY) else None
-        db = torch.empty(N, dtype=torch.float32, device=a.device) if b is not None and \
-            ctx.needs_input_grad[3] else None
-        nat.check(nat.lib().mi_elementwise_entropy(
-            family, a.data_ptr(), a_s, nat.ptr(b), b_s, N, out.data_ptr(), nat.ptr(da),
-            nat.ptr(db), nat.stream_handle(a.device)), "mi_elementwise_entropy")
-        ctx.grads = (da, db)
-        return out
-
-    @staticmethod
-    def backward(ctx, g: torch.Tensor):  # type: ignore[override]
-        da, db = ctx.grads
-        return None, None if da is None else da * g, None, None if db is None else db * g, None
+    (mi_elementwise_entropy)."""
+    N = a.shape[0]
+    out = torch.empty((), dtype=torch.float32, device=a.device)
+    # (the entropy of a Laplace or Cauchy factor does not depend on its loc)
+    da = torch.empty(N, dtype=torch.float32, device=a.device) if needs[1] and \
+        family not in (nat.PRED_LAPLACE, nat.PRED_CAUCHY) else None
+    db = torch.empty(N, dtype=torch.float32, device=a.device) if b is not None and \
+        needs[3] else None
+    nat.check(nat.lib().mi_elementwise_entropy(
+        family, a.data_ptr(), a_s, nat.ptr(b), b_s, N, out.data_ptr(), nat.ptr(da),
+        nat.ptr(db), nat.stream_handle(a.device)), "mi_elementwise_entropy")
+    return out, (None, da, None, db, None)
 
 
 def elementwise_entropy(distribution) -> torch.Tensor:
     """The summed entropy of a :func:`native_elementwise` guide factor (0-d, differentiable)."""
     N = max(1, int(distribution.batch_shape.numel()))
-    return _ElementwiseEntropyFn.apply(*_elementwise_params(distribution, N))
+    return _EntropyFn.apply(_elementwise_entropy, *_elementwise_params(distribution, N))
 
 
-def elementwise_draws() -> int:
-    return _DRAWS["elementwise"]
+# ---- the family table --------------------------------------------------------------------------
+@dataclasses.dataclass(frozen=True)
+class Family:
+    """A family of guide factors beyond Normal, Beta and Gamma with a native sampler."""
+    counter: str        # the key in _DRAWS; counts()["<counter>_draws"]
+    accepts: Callable   # (distribution) -> whether the native sampler draws it
+    sampler: _Sampler
+    # (distribution) -> (the sampler's inputs, the shape after K of the noise injected, that of
+    # the result)
+    prepare: Callable
+    # (distribution) -> its summed entropy by the family's own kernel; None: the ELBO kernels
+    # evaluate it (engine.entropy_factors), or else torch
+    entropy: Optional[Callable]
+
+
+# read by draw(), entropy() and counts()
+FAMILIES: Tuple[Family, ...] = (
+    Family("mvn", native_mvn, _MVN, _mvn_inputs, None),
+    Family("dirichlet", native_dirichlet, _DIRICHLET, _dirichlet_inputs, dirichlet_entropy),
+    Family("lowrank", native_lowrank, _LOWRANK, _lowrank_inputs, lowrank_entropy),
+    Family("elementwise", native_elementwise, _ELEMENTWISE_SAMPLER, _elementwise_inputs,
+           elementwise_entropy),
+)
+
+
+def entropy(factor: Distribution) -> torch.Tensor:
+    """The summed entropy of a guide factor the ELBO kernels do not evaluate
+    (engine.entropy_factors' rest): by the family's own kernel where it has one, else torch's."""
+    for family in FAMILIES:
+        if family.entropy is not None and family.accepts(factor):
+            return family.entropy(factor)
+    return factor.entropy().sum()
+
+
+def counts() -> Dict[str, int]:
+    """Factors each family's native sampler drew in the last draw_all, and LowRankMultivariateNormal
+    factors whose entropy mi_lowrank_entropy evaluated since
+    (EvidenceLowerBoundLoss.last_fusions merges them)."""
+    return {**{family.counter + "_draws": _DRAWS[family.counter] for family in FAMILIES},
+            "lowrank_entropies": _DRAWS["lowrank_entropy"]}
 
 
 # ---- deferred small Normal draws ---------------------------------------------------------------
@@ -821,34 +778,30 @@ class PendingDraw:
         self.done = True
         cfg, loc, scale, z = self.cfg, self.loc, self.scale, self.z
         K, N = z.shape
-        seed, step = _philox_key(cfg)
         if self.source is not None:
             # the guide's exp transform and the draw in one launch
             pending, u_ptr = self.source
             nat.check(nat.lib().mi_normal_rsample_exp(
-                loc.data_ptr(), self.loc_s, u_ptr, self.scale_s, scale.data_ptr(), K, N, seed,
-                step, nat.ptr(cfg.step_device), cfg.stream_id, cfg.particle_offset,
-                cfg.element_offset, nat.ptr(cfg.noise), z.data_ptr(),
-                nat.stream_handle(loc.device)), "mi_normal_rsample_exp")
+                loc.data_ptr(), self.loc_s, u_ptr, self.scale_s, scale.data_ptr(), K, N,
+                *philox_key(cfg, element=True), z.data_ptr(), nat.stream_handle(loc.device)),
+                "mi_normal_rsample_exp")
             pending.filled = True
         else:
             fill_exp(scale)
             nat.check(nat.lib().mi_normal_rsample(
-                loc.data_ptr(), self.loc_s, scale.data_ptr(), self.scale_s, K, N, seed, step,
-                nat.ptr(cfg.step_device), cfg.stream_id, cfg.particle_offset, cfg.element_offset,
-                nat.ptr(cfg.noise), z.data_ptr(), nat.stream_handle(loc.device)),
+                loc.data_ptr(), self.loc_s, scale.data_ptr(), self.scale_s, K, N,
+                *philox_key(cfg, element=True), z.data_ptr(), nat.stream_handle(loc.device)),
                 "mi_normal_rsample")
 
     def describe(self, D) -> None:
         """Fill an mi_draw descriptor for the linear site kernel that takes this draw over."""
-        cfg = self.cfg
-        seed, step = _philox_key(cfg)
-        D.operand, D.stream_id = 1, cfg.stream_id
+        D.operand = 1
         D.loc, D.loc_stride = self.loc.data_ptr(), self.loc_s
         D.scale, D.scale_stride = self.scale.data_ptr(), self.scale_s
         D.scale_exp = self.source[1] if self.source is not None else None
-        D.seed, D.step, D.step_device = seed, step, nat.ptr(cfg.step_device)
-        D.particle_offset, D.element_offset = cfg.particle_offset, cfg.element_offset
+        # (a deferred draw has no injected noise)
+        D.seed, D.step, D.step_device, D.stream_id, D.particle_offset, D.element_offset, _ = \
+            philox_key(self.cfg, element=True)
 
     def taken(self) -> None:
         """The linear launch made the draw (and the pending exp transform of its scale)."""
@@ -1078,46 +1031,21 @@ def draw(distribution: Distribution, cfg: DrawConfig, lazy: bool = False) -> tor
         nat.require_device(distribution.concentration, "guide Gamma concentration")
         conc, conc_s, rate, rate_s = gamma_params(distribution, N)
         _inject(cfg, conc.device, N)   # standard draws g, [K, *shape]
-        x = _GammaRsampleFn.apply(cfg, conc, conc_s, rate, rate_s)
+        # a deferred exp transform of the guide's parameters runs before the sampler reads them
+        # (no validation read has forced it when torch's argument validation is off, e.g. in a
+        # captured step)
+        fill_exp(conc)
+        fill_exp(rate)
+        x = _RsampleFn.apply(_GAMMA, cfg, conc, conc_s, rate, rate_s)
         return x.reshape((cfg.K,) + tuple(shape))
-    if native_mvn(distribution):
-        # the public properties: scale_tril carries the autograd of a covariance_matrix /
-        # precision_matrix parameterisation
-        D = int(distribution.event_shape[0])
-        loc = distribution.loc.reshape(D).contiguous()
-        scale_tril = distribution.scale_tril.reshape(D, D)
-        if scale_tril.dtype != torch.float32:
-            raise nat.NativeError(f"guide parameters must be float32, got {scale_tril.dtype}")
-        scale_tril = scale_tril.contiguous()
-        _inject(cfg, loc.device, D)   # eps, [K, D]
-        _DRAWS["mvn"] += 1
-        return _MvnRsampleFn.apply(cfg, loc, scale_tril)
-    if native_dirichlet(distribution):
-        conc = _dirichlet_rows(distribution)
-        N, C = conc.shape
-        _inject(cfg, conc.device, N, C)   # standard draws g, [K, *batch, C]
-        _DRAWS["dirichlet"] += 1
-        x = _DirichletRsampleFn.apply(cfg, conc)
-        return x.reshape((cfg.K,) + tuple(distribution.batch_shape) + (C,))
-    if native_lowrank(distribution):
-        # the public loc and the unbroadcast cov_factor / cov_diag (of an unbatched factor: the
-        # constructor's own arguments, which carry the autograd of the parameterisation)
-        cov_factor = distribution._unbroadcasted_cov_factor
-        cov_diag = distribution._unbroadcasted_cov_diag
-        fill_exp(cov_diag)
-        D, R = (int(n) for n in cov_factor.shape)
-        loc = distribution.loc.reshape(D).contiguous()
-        _inject(cfg, loc.device, D + R)   # eps_D | eps_W, [K, D + R]
-        _DRAWS["lowrank"] += 1
-        return _LowRankRsampleFn.apply(cfg, loc, cov_factor.contiguous(), cov_diag.contiguous())
-    if native_elementwise(distribution):
-        shape = distribution.batch_shape
-        N = max(1, int(shape.numel()))
-        family, a, a_s, b, b_s = _elementwise_params(distribution, N)
-        _inject(cfg, a.device, N)   # base noise (uniforms or normals), [K, *shape]
-        _DRAWS["elementwise"] += 1
-        z = _ElementwiseRsampleFn.apply(cfg, family, a, a_s, b, b_s)
-        return z.reshape((cfg.K,) + tuple(shape))
+    for family in FAMILIES:
+        if family.accepts(distribution):
+            inputs, noise_shape, shape = family.prepare(distribution)
+            _inject(cfg, inputs[family.sampler.params[0]].device, *noise_shape)
+            _DRAWS[family.counter] += 1
+            x = _RsampleFn.apply(family.sampler, cfg, *inputs)
+            # (a [K, D] draw is returned as it is, without a view node)
+            return x if x.shape[1:] == shape else x.reshape((cfg.K,) + shape)
     if cfg.noise is not None:
         return cfg.noise
     return distribution.rsample(torch.Size([cfg.K]))

@@ -667,14 +667,12 @@ class EvidenceLowerBoundLoss(nn.Module):
                 guide.release_lazy()
             if rest:
                 names = {id(f): name for name, f in approximation.items()}
-                # (a native Dirichlet factor: value and gradient by mi_dirichlet_entropy; a
-                # native one-noise-word factor: by mi_elementwise_entropy; a native
-                # LowRankMultivariateNormal factor: by mi_lowrank_entropy)
+                # (value and gradient by the family's own kernel where guide.FAMILIES has one)
                 extra = cast(torch.Tensor, sum(
-                    _rest_entropy(f) /
+                    guide.entropy(f) /
                     (world if shared is None or names[id(f)] in shared else 1)
                     for f in rest))
-                self.last_fusions["lowrank_entropies"] = guide.lowrank_entropies()
+                self.last_fusions["lowrank_entropies"] = guide.counts()["lowrank_entropies"]
                 engine.flush_pending_step()
                 loss = loss - extra
             if loss.is_cuda and loss.dim() == 0 and type(loss) is torch.Tensor:
@@ -692,18 +690,6 @@ class EvidenceLowerBoundLoss(nn.Module):
             else:
                 joint.raise_on_violation()
         return loss
-
-
-def _rest_entropy(factor: torch.distributions.Distribution) -> torch.Tensor:
-    """The summed entropy of a guide factor the ELBO kernels do not evaluate
-    (engine.entropy_factors' rest): by the family's own kernel where it has one, else torch's."""
-    if guide.native_dirichlet(factor):
-        return guide.dirichlet_entropy(factor)
-    if guide.native_elementwise(factor):
-        return guide.elementwise_entropy(factor)
-    if guide.native_lowrank(factor):
-        return guide.lowrank_entropy(factor)
-    return factor.entropy().sum()
 
 
 def _guide_device(approximation: Dict[str, torch.distributions.Distribution]) -> torch.device:

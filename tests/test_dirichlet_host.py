@@ -48,7 +48,7 @@ def test_native_dirichlet_declines():
         x = guide.draw(factor, cfg)
         torch.manual_seed(7)
         assert torch.equal(x, factor.rsample(torch.Size([5])))
-    assert guide.dirichlet_draws() == 0
+    assert guide.counts()["dirichlet_draws"] == 0
 
 
 def test_entry_points_declared_and_bound():

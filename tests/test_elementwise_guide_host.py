@@ -66,7 +66,7 @@ def test_declined_factors_keep_their_path(family):
     got = guide.draw(factor, config())
     torch.manual_seed(11)
     assert torch.equal(got, factor.rsample(torch.Size([K_HOST])))   # torch's generator
-    assert guide.elementwise_draws() == 0
+    assert guide.counts()["elementwise_draws"] == 0
 
 
 def test_header_symbols_are_exported():

@@ -117,8 +117,8 @@ def test_other_lowrank_factors_keep_the_torch_entropy():
     for name, factor in factors.items():
         assert not guide.native_lowrank(factor), name
         # the term the loss subtracts for a factor of the rest
-        assert torch.equal(nn._rest_entropy(factor), factor.entropy().sum()), name
-    assert guide.lowrank_entropies() == 0
+        assert torch.equal(guide.entropy(factor), factor.entropy().sum()), name
+    assert guide.counts()["lowrank_entropies"] == 0
 
 
 def test_host_lowrank_guide_entropy_gradient_is_torchs():
@@ -129,8 +129,8 @@ def test_host_lowrank_guide_entropy_gradient_is_torchs():
                                           cov_diag=0.5 * torch.ones(D))
     factor = module()
     guide.draw_all({"theta": factor}, 4, seed=1, step=0, particle_offset=0)
-    nn._rest_entropy(factor).backward()
-    assert guide.lowrank_entropies() == 0
+    guide.entropy(factor).backward()
+    assert guide.counts()["lowrank_entropies"] == 0
     params = module.distribution_parameters
     assert params["loc"].grad is None or not params["loc"].grad.any()
     for name in ("cov_factor", "cov_diag"):

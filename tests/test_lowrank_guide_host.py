@@ -98,7 +98,7 @@ def test_other_lowrank_factors_keep_the_torch_path():
     samples = guide.draw_all(factors, K, seed=1, step=0, particle_offset=0)
     torch.manual_seed(3)
     want = {name: factor.rsample(torch.Size([K])) for name, factor in factors.items()}
-    assert guide.lowrank_draws() == 0
+    assert guide.counts()["lowrank_draws"] == 0
     for name in want:
         assert samples[name].device.type == "cpu"
         assert torch.equal(samples[name], want[name])
@@ -118,7 +118,7 @@ def test_host_lowrank_guide_evaluates_through_torch():
     assert fused == [] and rest == [factor]
     samples = guide.draw_all({"theta": factor}, K, seed=1, step=0, particle_offset=0)
     z = samples["theta"]
-    assert guide.lowrank_draws() == 0
+    assert guide.counts()["lowrank_draws"] == 0
     assert z.shape == (K, D) and z.grad_fn is not None
     value = z.square().sum() / K - sum(f.entropy().sum() for f in rest)
     value.backward()

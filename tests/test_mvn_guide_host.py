@@ -82,7 +82,7 @@ def test_host_and_batched_mvn_keep_the_torch_path():
     samples = guide.draw_all({"a": host, "b": batched}, K, seed=1, step=0, particle_offset=0)
     torch.manual_seed(3)
     want = {"a": host.rsample(torch.Size([K])), "b": batched.rsample(torch.Size([K]))}
-    assert guide.mvn_draws() == 0
+    assert guide.counts()["mvn_draws"] == 0
     for name in want:
         assert samples[name].device.type == "cpu"
         assert torch.equal(samples[name], want[name])

@@ -1,14 +1,17 @@
 """
 Time the one-noise-word guide factors: an eager ELBO evaluation and its backward of
 `sigma ~ Gamma(2, 2)` (D elements), `y ~ Normal(0, sigma)` under a D-element LogNormal guide at
-K = 256, natively drawn against torch's own rsample and entropy (the same code with
-guide.native_elementwise declining), variants alternating in one process, device events; and
+K = 256, natively drawn against torch's own rsample and entropy (the same code with the
+``accepts`` of the family's record in guide.FAMILIES declining; the table is what guide.draw and
+guide.entropy read, so the record is swapped, not guide.native_elementwise), variants alternating
+in one process, device events; and
 mi_elementwise_rsample + mi_elementwise_rsample_backward alone for every family at K = 4096,
 N = 65536 (1 GiB of draws), as achieved bytes per second: z written, dz read. Prints one JSON line
 per measurement.
 """
 import argparse
 import ctypes
+import dataclasses
 import json
 import os
 import statistics
@@ -97,18 +100,20 @@ def main():
     parser.add_argument("--launch-elements", type=int, default=65536)
     args = parser.parse_args()
     device = torch.device("cuda")
-    native_elementwise = guide.native_elementwise
+    families = guide.FAMILIES
+    declining = tuple(dataclasses.replace(family, accepts=lambda distribution: False)
+                      if family.counter == "elementwise" else family for family in families)
     for D in args.sizes:
         K = args.particles
         native, native_loss = elbo_step(D, K, device)
         torch_path, torch_loss = elbo_step(D, K, device)
 
         def declined():
-            guide.native_elementwise = lambda distribution: False
+            guide.FAMILIES = declining
             try:
                 return torch_path()
             finally:
-                guide.native_elementwise = native_elementwise
+                guide.FAMILIES = families
 
         for fn in (native, declined):
             timed(fn, 10)

@@ -1,14 +1,17 @@
 """
 Time a LowRankMultivariateNormal guide: an eager ELBO evaluation and its backward
 of `theta ~ Normal(0, 1)` with D elements, K = 256, R = 16, natively drawn and its entropy native
-("native"), natively drawn with torch's own entropy ("torch_entropy": the same code with
-guide.lowrank_entropy replaced by torch's), and torch's own rsample and entropy ("torch": the same
-code with guide.native_lowrank declining), variants alternating in one process, device events; and
+("native"), natively drawn with torch's own entropy ("torch_entropy": the same code with the
+entropy of the family's record in guide.FAMILIES replaced by torch's), and torch's own rsample and
+entropy ("torch": the same code with that record's ``accepts`` declining; the table is what
+guide.draw and guide.entropy read, so the records are swapped, not the module's functions),
+variants alternating in one process, device events; and
 mi_lowrank_rsample, mi_lowrank_rsample_backward and mi_lowrank_entropy (value and gradients)
 alone. Prints one JSON line per D.
 """
 import argparse
 import ctypes
+import dataclasses
 import json
 import os
 import statistics
@@ -94,7 +97,13 @@ def main():
     parser.add_argument("--steps", type=int, default=20)
     args = parser.parse_args()
     device = torch.device("cuda")
-    native_lowrank, lowrank_entropy = guide.native_lowrank, guide.lowrank_entropy
+    families = guide.FAMILIES
+
+    def swapped(**fields):
+        """guide.FAMILIES with the LowRankMultivariateNormal record's fields replaced."""
+        return tuple(dataclasses.replace(family, **fields) if family.counter == "lowrank"
+                     else family for family in families)
+
     for D in args.sizes:
         R, K = args.rank, args.particles
         native, native_loss = elbo_step(D, R, K, device)
@@ -102,18 +111,18 @@ def main():
         entropy_path, entropy_loss = elbo_step(D, R, K, device)
 
         def torch_entropy():   # the native draw with the entropy autograd walks the constructor for
-            guide.lowrank_entropy = lambda distribution: distribution.entropy().sum()
+            guide.FAMILIES = swapped(entropy=lambda distribution: distribution.entropy().sum())
             try:
                 return entropy_path()
             finally:
-                guide.lowrank_entropy = lowrank_entropy
+                guide.FAMILIES = families
 
         def declined():
-            guide.native_lowrank = lambda distribution: False
+            guide.FAMILIES = swapped(accepts=lambda distribution: False)
             try:
                 return torch_path()
             finally:
-                guide.native_lowrank = native_lowrank
+                guide.FAMILIES = families
 
         for fn in (native, torch_entropy, declined):
             timed(fn, 10)
