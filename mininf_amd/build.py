@@ -18,7 +18,8 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(ROOT, "include")
 SOURCES = [os.path.join(CSRC, name)
-           for name in ("sites.hip", "guide.hip", "elbo.hip", "linear.hip", "softmax_linear.hip", "gather_site.hip",
+           for name in ("sites.hip", "bcast_site.hip", "reduce.hip", "categorical.hip",
+                        "guide.hip", "elbo.hip", "linear.hip", "softmax_linear.hip", "gather_site.hip",
                         "gather_linear_site.hip",
                         "minibatch.hip",
                         "adam.hip", "mvn.hip", "mvn_guide.hip", "lowrank_guide.hip", "lowrank_entropy.hip",

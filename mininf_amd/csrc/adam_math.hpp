@@ -1,5 +1,6 @@
-// Adam arithmetic shared by the one-launch optimizer step (adam.hip) and the launches that finish
-// a whole training step themselves (linear.hip lin_finish, sites.hip bcast_finish): restated from
+// Adam arithmetic shared by the one-launch optimizer step (adam.hip) and the launch that finishes
+// a whole training step itself (the ELBO forward's tail, elbo.hip; no site unit -- sites.hip,
+// bcast_site.hip, linear.hip -- finishes a step any more): restated from
 // torch's fused Adam (ATen/native/cuda/fused_adam_utils.cuh adam_math, ADAM_MODE::ORIGINAL, no
 // AMSGrad) -- hyper-parameters in double, moments and parameter in float, bias corrections
 // 1 - beta^step in double: bit-identical to torch.optim.Adam(fused=True).

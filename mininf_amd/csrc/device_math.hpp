@@ -1,4 +1,5 @@
-// Device math shared by the precompiled kernels (sites.hip) and the site programs specialised at
+// Device math shared by the precompiled kernels (sites.hip, bcast_site.hip and the other units of
+// build.py's SOURCES) and the site programs specialised at
 // trace time with hiprtc (jit.cpp embeds this file verbatim): family log-densities and their
 // derivatives, special functions, wavefront reductions. No includes beyond mininf_amd.h so that it
 // compiles both under hipcc (after hip_runtime.h) and under hiprtc.

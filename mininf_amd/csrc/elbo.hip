@@ -517,7 +517,7 @@ __shared__ unsigned long long mi_ets[16];
 // ---- deferred site finalize reductions (mi_elbo.reduce) ---------------------------------------
 // Block (job a, particle block kb, value v) sums part[v][seg][k] over the job's segments for 64
 // particles: 4 segment groups of 64 lanes, up to sixteen loads in flight per lane, partial sums in fp64
-// combined in a fixed order -- the arithmetic of sites.hip k_finalize, fused into this launch.
+// combined in a fixed order -- the arithmetic of reduce.hip k_finalize, fused into this launch.
 // Jobs with one site value split their values over blocks (as k_finalize's split mode).
 // Long segment lists use blocks of 32 particles x 8 segment groups (more blocks, fewer serial load
 // rounds per lane; MININF_AMD_ELBO_KRED), short ones 64 particles x 4 groups.
@@ -1670,8 +1670,9 @@ Layout make_layout(const mi_elbo* e) {
     // long lists over few particles (a fused draw's block rows: ~1000 segments, K = 128): 16
     // particles x 16 segment groups per block, for more blocks and fewer serial loads per lane
     // (very long lists, C5's 977 block rows: 8 particles per block, two rounds of loads per lane
-    // instead of four -- 0.3 us per C5 step, tools/gpurun_r05/t29.sh; C4's 513 keep 16: 8 was
-    // 1.1 us slower there in r04)
+    // instead of four -- 0.3 us per C5 step in r05; the launch that writes those rows is the
+    // planned one of profiles/r06_ab.json ab8_c5gy3, the first 16-against-8 runs are
+    // profiles/r03_ab.json kred_*; C4's 513 keep 16: 8 was 1.1 us slower there in r04)
     L.red.kred[r] = (J.nseg >= 768 && J.K < 2048)                       ? 8
                     : (J.nseg >= 512 && J.K < 2048)                     ? kKredLong
                     : (J.nseg >= 64 && kKred != mi::kRedKWide) ? kKred

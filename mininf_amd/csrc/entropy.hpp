@@ -1,5 +1,5 @@
-// fp32 digamma / trigamma and the Beta entropy terms of the ELBO tail, shared by the ELBO kernels
-// (elbo.hip) and the site launches that finish the ELBO themselves (sites.hip).
+// fp32 digamma / trigamma and the Beta entropy terms of the ELBO tail (elbo.hip; the site units,
+// sites.hip and bcast_site.hip, no longer finish the ELBO themselves and do not include this).
 #pragma once
 
 #include "common.hpp"

@@ -46,7 +46,7 @@ inline float* slice_out(float* out, void* workspace, int64_t slices, int64_t off
   return slices > 1 ? static_cast<float*>(workspace) + offset : out;
 }
 
-// Fixed-order fp64 reduction of per-(segment, particle) partials part[v][nseg][K] (sites.hip
+// Fixed-order fp64 reduction of per-(segment, particle) partials part[v][nseg][K] (reduce.hip
 // k_finalize): values v < num_sites are multiplied by scale[v] and summed into total[k] (and
 // written to site_lp[v*K + k] when non-NULL); the remaining num_slots values are multiplied by
 // slot_scale and written to slot_grad[(v - num_sites)*K + k].
@@ -66,6 +66,11 @@ int mi_launch_finalize(const float* part, int64_t nseg, int64_t K, int num_sites
 // jobs itself (its lead blocks then add the job's doubles).
 struct mi_reduce;
 int mi_reduce_launch_slots(const mi_reduce* r, void* stream);
+
+// The per-K-block dloc / dscale partials of a fused guide draw, part[2][slices][N], summed over the
+// slices in a fixed order (reduce.hip k_draw_reduce).
+int mi_launch_draw_reduce(const float* part, int64_t slices, int64_t N, float* dloc, float* dscale,
+                          hipStream_t stream);
 
 // Timing events around a site kernel (the `start_event` / `stop_event` arguments) are for eager
 // launches only. Round 5 first recorded them under capture with hipEventRecordWithFlags(...,

@@ -124,7 +124,8 @@ std::string mask_kind_tag(const mi_site& st) {
 
 // MININF_AMD_DRAW_PAIRS=1: the fused-draw accumulator loop takes two particles per iteration as
 // two independent Philox -> Box-Muller -> density chains (opt-in: measured slower on MI355X, round
-// 6 -- C5's program 153.4-154.0 us against 151.7-152.5 with one chain, profiles/r06_c5_ab.json).
+// 6 -- C5's program 153.4-154.0 us against 151.7-152.5 with one chain, profiles/r06_ab.json
+// ab2_c5pair / ab2_c5base).
 // Read per compile; part of the signature.
 bool draw_pairs() {
   const char* v = std::getenv("MININF_AMD_DRAW_PAIRS");

@@ -40,7 +40,7 @@ MF_STAGE_ROWS = 128       # rows per stage with one feature tile (MfShape::CH = 
 MF_TARGET_BLOCKS = 1024   # blocks aimed at over the grid (divided by gy)
 VALU_CHUNK = 64           # kLinChunk
 VALU_TARGET_BLOCKS = 768
-FIN_CHUNK = 256           # kFinChunk (csrc/sites.hip): chunked finalize above 2 * FIN_CHUNK tiles
+FIN_CHUNK = 256           # kFinChunk (csrc/reduce.hip): chunked finalize above 2 * FIN_CHUNK tiles
 
 
 def ceil_div(a, b):

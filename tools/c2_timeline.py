@@ -1,9 +1,9 @@
 """
 Where C2's site kernel (k_site_bcast_smem, the matrix instantiation) spends its time, per workgroup:
-a build of sites.hip with MI_SITES_TIMELINE defined, in which thread 0 of every workgroup stamps
+a build of bcast_site.hip with MI_SITES_TIMELINE defined, in which thread 0 of every workgroup stamps
 the constant-rate clock (s_memrealtime, 100 MHz) at entry, after the per-particle logits, after the
 chunk pass and its barrier round, after the first matrix pass, after the matrix loop, after the
-chunks' values are stored and at exit (the MI_TL points of sites.hip).
+chunks' values are stored and at exit (the MI_TL points of bcast_site.hip).
 `run` replays the C2 bench step (24 steps per graph replay, as bench.py), then one more replay with
 the rows cleared, and prints the phase statistics of the last launch of that replay -- by dispatch
 rank on the CU (block b is the b / 256-th workgroup of its CU), for the particle-constant
@@ -31,15 +31,15 @@ from mininf_amd.graph import StepGraph  # noqa: E402
 
 
 def build_variant(name="c2tl"):
-    """The timeline build of the tree's sites.hip, through tools/variant_build.py."""
+    """The timeline build of the tree's bcast_site.hip, through tools/variant_build.py."""
     import subprocess
     import tempfile
-    src = open(os.path.join(ROOT, "mininf_amd", "csrc", "sites.hip")).read()
+    src = open(os.path.join(ROOT, "mininf_amd", "csrc", "bcast_site.hip")).read()
     with tempfile.TemporaryDirectory() as tmp:
-        path = os.path.join(tmp, "sites.hip")
+        path = os.path.join(tmp, "bcast_site.hip")
         open(path, "w").write("#define MI_SITES_TIMELINE 1\n" + src)
         subprocess.run([sys.executable, os.path.join(ROOT, "tools", "variant_build.py"), name,
-                        f"sites.hip={path}"], check=True)
+                        f"bcast_site.hip={path}"], check=True)
 
 
 def main():
