@@ -551,6 +551,60 @@ int mi_lowrank_entropy(const float* cov_factor, const float* cov_diag,
                        void* workspace, size_t workspace_bytes,
                        float* entropy, float* dcov_factor, float* dcov_diag, void* stream);
 
+/* LowRankMultivariateNormal site density (replaces LowRankMultivariateNormal.log_prob, torch 2.10
+ * lowrank_multivariate_normal.py:203-212) for K particles and N rows, and its gradients in closed
+ * form. All float32; every parameter is read through a particle stride, which may be 0:
+ *   value[k, i, :]  at value + k value_stride_k + i value_stride_i, the last axis contiguous
+ *                   (value_stride_k = 0: observed data the particles share),
+ *   loc[k, :], W = cov_factor[k][D, R] row-major, d = cov_diag[k, :] > 0 and
+ *   L = capacitance_tril[k][R, R], the lower Cholesky factor of C = I + W^T diag(1 / d) W that the
+ *   constructor keeps as _capacitance_tril (only its lower triangle is read).
+ * Forward, per (k, i), with r = x_i - loc, y = r / d, t = W^T y and c = C^-1 t:
+ *   log_prob[k, i] = -1/2 (D log 2 pi + 2 sum_j log L[j, j] + sum_j log d[j] + r.y - t.c)
+ *   coef[k, i, :]  = c                                       ([K, N] and [K, N, R], contiguous)
+ * B = L^-1 is formed per particle in fp64 and handed on as f32, and c = B^T (B t), t.c = |B t|^2:
+ * C^-1 itself is never formed (for R > D its product with t loses to rounding what r - W c then
+ * cancels against). Both log sums are fp64, and T = Y W is one pass over the rows (on
+ * v_mfma_f32_32x32x2_f32 for R >= 32, zero-padded to whole tiles; on the vector pipe below that).
+ * Two launches.
+ * Backward, for the upstream g[k, i] at g + k g_stride_k + i g_stride_i and the forward's coef, with
+ * a_i = (r_i - W c_i) / d, G_k = sum_i g[k, i] and M = W C^-1:
+ *   dvalue[k, i, :]   = -g_i a_i                                             [K, N, D]
+ *   dloc[k, :]        = sum_i g_i a_i                                        [K, D]
+ *   dcov_factor[k]    = sum_i g_i a_i c_i^T - G_k M / d[:, None]             [K, D, R]
+ *   dcov_diag[k, j]   = 1/2 sum_i g_i a_ij^2
+ *                       - 1/2 G_k (1 / d_j - (sum_r M[j, r] W[j, r]) / d_j^2) [K, D]
+ * (contiguous) -- the whole derivatives with respect to W and d, L's dependence on them included:
+ * nothing is to be propagated into capacitance_tril. Each of the four may be NULL and is then not
+ * computed; the others are bit-identical to those of the call that asks for all four. A row with
+ * g_i == 0 contributes exact zeros everywhere, whatever its value holds (NaN included). The row
+ * sums have a fixed order: per-slice partials in the workspace, each a chain in row order, summed
+ * in slice order by a finishing launch (no atomics: two calls on the same inputs are
+ * bit-identical). 1 <= R <= MI_LOWRANK_MAX_R, 1 <= D <= MI_LOWRANK_SITE_MAX_D and K * D and
+ * K * ceil(N / 32) within a grid's 2^31 - 1 blocks (beyond: MI_EUNSUPPORTED); K, N, D or R < 1, a NULL
+ * required pointer or a workspace smaller than mi_lowrank_site_workspace_bytes asks for (one size
+ * serves both calls): MI_EINVAL. All checked before any device work. */
+#define MI_LOWRANK_SITE_MAX_D (1 << 16)
+int mi_lowrank_site_workspace_bytes(int64_t K, int64_t N, int64_t D, int64_t R, size_t* bytes);
+int mi_lowrank_site_forward(const float* value, int64_t value_stride_k, int64_t value_stride_i,
+                            const float* loc, int64_t loc_stride_k,
+                            const float* cov_factor, int64_t cov_factor_stride_k,
+                            const float* cov_diag, int64_t cov_diag_stride_k,
+                            const float* capacitance_tril, int64_t capacitance_tril_stride_k,
+                            int64_t K, int64_t N, int64_t D, int64_t R,
+                            void* workspace, size_t workspace_bytes,
+                            float* log_prob, float* coef, void* stream);
+int mi_lowrank_site_backward(const float* g, int64_t g_stride_k, int64_t g_stride_i,
+                             const float* value, int64_t value_stride_k, int64_t value_stride_i,
+                             const float* loc, int64_t loc_stride_k,
+                             const float* cov_factor, int64_t cov_factor_stride_k,
+                             const float* cov_diag, int64_t cov_diag_stride_k,
+                             const float* capacitance_tril, int64_t capacitance_tril_stride_k,
+                             const float* coef, int64_t K, int64_t N, int64_t D, int64_t R,
+                             void* workspace, size_t workspace_bytes,
+                             float* dvalue, float* dloc, float* dcov_factor, float* dcov_diag,
+                             void* stream);
+
 /* Beta(concentration1, concentration0) draws x[k, i] = G1 / (G1 + G0) with Marsaglia-Tsang gamma
  * variates from the same counter-based generator (beta.py:85-86, dirichlet.py:23-36, 85-88). With
  * `x_in` non-NULL the draws are copied from it instead (parity mode). */

@@ -33,6 +33,7 @@ DIRICHLET_MAX_C = 1024   # MI_DIRICHLET_MAX_C
 MIXTURE_MAX_C = 1024   # MI_MIXTURE_MAX_C
 LOWRANK_MAX_R = 128   # MI_LOWRANK_MAX_R
 LOWRANK_MAX_D = 1 << 24   # MI_LOWRANK_MAX_D
+LOWRANK_SITE_MAX_D = 1 << 16   # MI_LOWRANK_SITE_MAX_D
 PRED_CATEGORICAL_MAX_C = 1024   # MI_PRED_CATEGORICAL_MAX_C
 # MI_PRED_* family codes of mi_predictive_sample
 (PRED_BERNOULLI_PROBS, PRED_BERNOULLI_LOGITS, PRED_EXPONENTIAL, PRED_LAPLACE, PRED_CAUCHY,
@@ -405,6 +406,15 @@ _SIGNATURES = {
         c_i64, c_i64, ctypes.POINTER(ctypes.c_size_t)]),
     "mi_lowrank_entropy": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, ctypes.c_size_t,
                                           c_vp, c_vp, c_vp, c_vp]),
+    "mi_lowrank_site_workspace_bytes": (ctypes.c_int, [
+        c_i64, c_i64, c_i64, c_i64, ctypes.POINTER(ctypes.c_size_t)]),
+    "mi_lowrank_site_forward": (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp,
+                                               c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64,
+                                               c_vp, ctypes.c_size_t, c_vp, c_vp, c_vp]),
+    "mi_lowrank_site_backward": (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp,
+                                                c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
+                                                c_vp, c_i64, c_i64, c_i64, c_i64, c_vp,
+                                                ctypes.c_size_t, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mi_beta_rsample": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, ctypes.c_uint64,
                                        ctypes.c_uint64, c_vp, ctypes.c_uint32, c_i64, c_vp, c_vp,
                                        c_vp]),

@@ -23,6 +23,7 @@ SOURCES = [os.path.join(CSRC, name)
                         "gather_linear_site.hip",
                         "minibatch.hip",
                         "adam.hip", "mvn.hip", "mvn_guide.hip", "lowrank_guide.hip", "lowrank_entropy.hip",
+                        "lowrank_site.hip",
                         "dirichlet.hip", "mixture.hip", "predictive.hip", "elementwise_guide.hip", "peer.hip", "jit.cpp")]
 # every header: a change to any of them rebuilds every object
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + [os.path.join(INCLUDE, "mininf_amd.h")]

@@ -18,6 +18,7 @@
 // Without gradient outputs launch 1 only sums the logs and launch 2 only log d. Every sum has a
 // fixed order (no atomics): two calls on the same inputs are bit-identical.
 #include "internal.hpp"
+#include "lowrank_capacitance.hpp"
 #include "mfma_tile.hpp"
 
 #include <algorithm>
@@ -27,12 +28,7 @@ namespace mi {
 constexpr int kLeRowThreads = 256;         // the VALU row pass: a row per thread
 constexpr int kLeSumThreads = 256;         // the finish
 
-// ---- 1. the R x R stage ----------------------------------------------------------------------
-// One fp64 array X[R][ld] (ld odd: rows and columns both conflict-free) carries everything: at the
-// start its strict upper triangle holds L^T (X[k][i] = L[i][k], i > k), its diagonal 1 / L[k][k]
-// and its strict lower triangle the right-hand side I (zeros: the unit diagonal is implied). Step k
-// reads only row k -- the unscaled row k of L^-1 to its left, column k of L to its right -- and
-// updates the rows below it, so one barrier separates the steps.
+// ---- 1. the R x R stage (lowrank_capacitance.hpp) -----------------------------------------------
 __global__ __launch_bounds__(1024) void k_lowrank_entropy_capacitance(
     const float* __restrict__ L, int R, int inverse, float* __restrict__ cinv,
     double* __restrict__ logdet) {
@@ -40,19 +36,8 @@ __global__ __launch_bounds__(1024) void k_lowrank_entropy_capacitance(
   const int ld = R | 1;
   double* lg = X + R * ld;
   const int t = threadIdx.x, nt = blockDim.x;
-  const int tx = t & (kWave - 1), ty = t >> 6, ny = nt >> 6;
   for (int j = t; j < R; j += nt) lg[j] = log((double)L[j * R + j]);
-  if (inverse) {
-    for (int e = t; e < R * R; e += nt) {
-      const int r = e / R, c = e - r * R;
-      if (c < r) {
-        X[c * ld + r] = (double)L[e];
-        X[r * ld + c] = 0.0;
-      } else if (c == r) {
-        X[r * ld + r] = 1.0 / (double)L[e];
-      }
-    }
-  }
+  if (inverse) capacitance_stage(L, R, X);
   __syncthreads();
   if (t == 0) {
     double s = 0.0;
@@ -60,39 +45,7 @@ __global__ __launch_bounds__(1024) void k_lowrank_entropy_capacitance(
     *logdet = s;
   }
   if (!inverse) return;   // (block-uniform)
-  for (int k = 0; k + 1 < R; ++k) {
-    const double rk = X[k * ld + k];
-    for (int j = tx; j <= k; j += kWave) {
-      const double xk = j == k ? rk : X[k * ld + j] * rk;   // L^-1[k][j]
-      for (int i = k + 1 + ty; i < R; i += ny)
-        X[i * ld + j] = fma(-X[k * ld + i], xk, X[i * ld + j]);
-    }
-    __syncthreads();
-  }
-  // the rows scaled: X = L^-1, zero above the diagonal
-  for (int e = t; e < R * R; e += nt) {
-    const int i = e / R, j = e - i * R;
-    if (j < i) X[i * ld + j] *= X[i * ld + i];
-    else if (j > i) X[i * ld + j] = 0.0;
-  }
-  __syncthreads();
-  // C^-1[a][b] = sum_i X[i][a] X[i][b], i ascending (the terms with i < max(a, b) are zeros, so
-  // [a][b] and [b][a] are the same sum)
-  for (int a0 = ty * 8; a0 < R; a0 += ny * 8) {
-    for (int b = tx; b < R; b += kWave) {
-      double acc[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) acc[u] = 0.0;
-      for (int i = a0; i < R; ++i) {
-        const double xb = X[i * ld + b];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc[u] = fma(X[i * ld + min(a0 + u, R - 1)], xb, acc[u]);
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (a0 + u < R) cinv[(a0 + u) * R + b] = (float)acc[u];
-    }
-  }
+  capacitance_invert(X, R, cinv);
 }
 
 // The block's fp64 sum, threads in a fixed tree: partial[blockIdx.x].

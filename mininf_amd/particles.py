@@ -30,6 +30,7 @@ import torch
 from torch.distributions import Bernoulli, Beta, Binomial, Categorical, Cauchy, Dirichlet, \
     Distribution, \
     Exponential, ExpTransform, Gamma, HalfCauchy, HalfNormal, Laplace, LogNormal, \
+    LowRankMultivariateNormal, \
     MixtureSameFamily, MultivariateNormal, NegativeBinomial, Normal, Poisson, PowerTransform, StudentT, \
     TransformedDistribution
 from torch.distributions.constraints import Constraint
@@ -37,7 +38,7 @@ from torch.distributions.utils import lazy_property
 from torch.overrides import TorchFunctionMode
 from torch.utils._pytree import tree_flatten, tree_map
 
-from . import _native, core, data, graph, mvn, predictive, switches
+from . import _native, core, data, graph, lowrank_site, mvn, predictive, switches
 from .distributions import InverseGamma
 from .core import batch, no_log_prob, State, TracerMixin, Value, validate_shape
 from .util import _normalize_shape, check_constraint, OptionalSize
@@ -767,8 +768,17 @@ class ParticleTracer(TracerMixin):
                 log_prob = mvn.log_prob(distribution, data).float()
             else:
                 log_prob = distribution.log_prob(data.double()).float()
+        elif isinstance(data, torch.Tensor) and data.dtype == torch.float32 and \
+                data.device.type != "cpu" and lowrank_site.enabled(distribution):
+            # mi_lowrank_site_forward: one launch for all particles, closed-form gradients
+            log_prob = lowrank_site.log_prob(distribution, data)
         else:
             log_prob = distribution.log_prob(data)
+        if mask is not None and isinstance(distribution, LowRankMultivariateNormal) and \
+                mask.dim() == log_prob.dim() + 1:
+            # an observation masked entry by entry, [N, D]: a row is observed when all its entries
+            # are (on the kernels and on torch's log_prob alike)
+            mask = mask.all(-1)
         if mask is not None:
             log_prob = torch.where(mask, log_prob, torch.zeros((), dtype=log_prob.dtype,
                                                                device=log_prob.device))
@@ -902,6 +912,9 @@ def _trace(model: Callable, samples: Dict[str, torch.Tensor], K: int, validate: 
                 stack.enter_context(torch.device(lift))
             if compat:
                 stack.enter_context(TraceCompat(lift, tracer))
+            elif switches.enabled("LOWRANK_SITE"):
+                # (TraceCompat sends every factorisation to mi_cholesky itself)
+                stack.enter_context(lowrank_site.ConstructorCholesky())
             if mode is not None:
                 with mode:
                     core.condition(model, **dict(zip(names, values)))()

@@ -21,6 +21,7 @@ SWITCHES = {
     "DEFER_STEP": (True, "hold the step-finishing launch for the optimizer step"),
     "MVN_KERNEL": (True, "native MultivariateNormal log density"),
     "CHOLESKY_KERNEL": (True, "native batched Cholesky factorisation"),
+    "LOWRANK_SITE": (True, "native LowRankMultivariateNormal site density and gradients"),
     "DEFER_MATMUL": (True, "leave a model's X @ theta to the linear site kernel"),
     "DEFER_GATHER": (True, "leave a model's alpha[group] to the gathered site kernel"),
     "DEFER_SUM": (True, "leave a model's alpha[group] + X @ theta to the gathered linear site "
